@@ -7,23 +7,31 @@ temporal off, cap 20.  A "step" is one frame of the hot path (SimpleGuiDX11::pro
 pg/simpleguidx11.cpp:359-487): G-buffer + initial RIS, spatial reuse, shade.  Scene + buffers are
 resident in HBM before timing; the framebuffer stays in HBM (zero-copy, rs_get_frame_device_ptr).
 
-N=1 also measures, under "configs" of the same JSON line, the other single-GPU configs (C3 Sponza-like
+A plain run does only what the headline figure needs: scene load, traversal tuning, --warmup frames, the
+--steps timed frames, and one JSON line (value, ms_per_step, Mrays/s, the frame roofline).  --dump-outputs DIR
+then writes what the last timed step left for its caller -- the framebuffer, DIR/frame.npy, (H, W, 3)
+float32 -- so that two builds can be compared output for output (scenes, cameras and the per-pixel RNG are
+seeded: the same arguments give the same inputs).
+
+--full adds everything else.  N=1: the kernel window of the headline config (kernel_roofline, limiter), its
+bounded CPU baseline and, under "configs" of the same JSON line, the other single-GPU configs (C3 Sponza-like
 with temporal reuse, the full 240-frame C5 sequence, C2V = doVisibilityPass, C4_1gpu = C3 at 3840x2160 on
 one GPU -- the denominator of the C4 speed-up), each with its own ms_per_step, Mrays/s, rooflines and a
 bounded CPU baseline, the denoiser and the drop-in C++ host path (include/restir.hpp through
 tools/restir_render, framebuffer copied to host memory every frame).  The printed line is compact (every
 config's value, ms_per_step, rooflines and CPU baseline); the full record (per-pass times, host, limiter
-details, per-layer denoiser times) goes to gpurun_out/bench_full.json.
+details, per-layer denoiser times) goes to the file named by --full-out.
 
 N>1 (torchrun): the frame is split into N row bands (strong scaling, one process per GPU); reservoir
 halo rows are exchanged over RCCL before each spatial pass and the band framebuffers are gathered to
-rank 0 (csrc/rs_mgpu.hip).  The line carries the headline config (C2) and, under "configs", C4 (BASELINE
-configs[3]: the C3 scene at 3840x2160 across the N GPUs), each with its per-rank band / halo / gather times.
+rank 0 (csrc/rs_mgpu.hip).  The line carries the headline config (C2) and, with --full, under "configs", C4
+(BASELINE configs[3]: the C3 scene at 3840x2160 across the N GPUs), each with its per-rank band / halo /
+gather times.
 
 Frames are pipelined by the library (run-ahead lanes, up to 3 frames in flight); every frame is still
 rendered completely.  Rooflines (SURVEY.md §8(d) algorithmic bytes):
   roofline         the whole frame: B_px (480 B at C2) x pixels / ms_per_step
-  kernel_roofline  the dominant kernel alone: its §8(d) bytes (186 B/px for G-buffer + initial) /
+  kernel_roofline  (--full) the dominant kernel alone: its §8(d) bytes (186 B/px for G-buffer + initial) /
                    its launch time measured with HIP events in a second window with one frame in
                    flight (RESTIR_RUNAHEAD=0 semantics), flagged when that exceeds ms_per_step (the
                    pipelined frame hides the kernel's ramp-up and tail behind its neighbours)
@@ -96,8 +104,13 @@ def workload(name):
     return sc, prm, camera, light_pos
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: kernel window, CPU baselines, the other configs, denoiser, "
+                         "drop-in host path and the full record (see --no-cpu-baseline, --no-extras)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's framebuffer as DIR/frame.npy (float32)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -105,14 +118,15 @@ def parse():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--scene", default="C2", choices=list(WORKLOADS))
     ap.add_argument("--multi-configs", default="C4",
-                    help="N>1: further configs measured after --scene in the same run (comma list, '' for none)")
+                    help="N>1 with --full: further configs measured after --scene in the same run (comma list, '' "
+                         "for none)")
     ap.add_argument("--full-out", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"),
                     help="the full record (the printed line is compact)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="N=1: skip the C3/C5/C2V and drop-in lines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N=1: skip the C3/C5/C2V and drop-in lines")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="oracle threads for the CPU baseline; 0 = every core available to this process")
-    return ap.parse_args()
+    return ap.parse_args(argv)
 
 
 def host_cpu():
@@ -276,8 +290,38 @@ def limiter_for(pmc, kernel):
             "cache_lines_per_vmem_load": v.get("cache_accesses_per_vmem_rd"), "source": pmc.get("_path")}
 
 
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_BYTES_MAX = 64 * 1000 * 1000
+
+
+def device_frame(ptr, W, H):
+    """Host copy of a device framebuffer (W*H*3 floats at `ptr`; the caller has synchronised the frame)."""
+    import torch
+
+    class _DeviceArray:
+        __cuda_array_interface__ = {"shape": (H * W * 3,), "typestr": "<f4", "data": (int(ptr), False), "version": 2,
+                                    "strides": None}
+    return torch.as_tensor(_DeviceArray(), device="cuda").cpu().numpy().reshape(H, W, 3)
+
+
+def dump_outputs(path, arrays):
+    """Writes every array as <path>/<name>.npy in float32 (float64 stays float64), DUMP_BYTES_MAX in all; a
+    larger array is cut to a fixed sample of its elements (seed 0, ascending flat indices)."""
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES_MAX // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > budget:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, budget // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, f"{name}.npy"), a)
+
+
 # ---------------------------------------------------------------- one single-GPU config
-def run_single(name, W, H, steps, warmup, device, stream, cpu_threads, with_cpu, kernel_frames=5):
+def run_single(name, W, H, steps, warmup, device, stream, cpu_threads, with_cpu, kernel_frames=5, full=True,
+               dump_dir=None):
+    """One config on one GPU.  full=False stops after the timed steps (and the dump): no kernel window, no
+    per-kernel figures, no CPU baseline."""
     from restir_amd import Renderer
     sc, prm, camera, light_pos = workload(name)
     r = Renderer(W, H, device=device, stream=stream)
@@ -307,22 +351,11 @@ def run_single(name, W, H, steps, warmup, device, stream, cpu_threads, with_cpu,
     tot, n_timed = r.timing_totals(reset=True)
     ms_per_step = dt / steps * 1e3
     rays = int(tot.rays)
-    # kernel window: one frame in flight (run-ahead 0), HIP events around every pass on the frame's stream
-    r.set_run_ahead(0)
-    for f in range(2):
-        step(warmup + steps + f)
-    r.timing_totals(reset=True)
-    for f in range(kernel_frames):
-        step(warmup + steps + 2 + f)
-    ktot, kn = r.timing_totals(reset=True)
-    r.set_run_ahead(2)
-    iso = {k: float(getattr(ktot, k)) / max(1, kn) for k in PASS_BYTES}
-    iso_total = float(ktot.total_ms) / max(1, kn)
-    dom = max(iso, key=iso.get)
+    if dump_dir:        # what the last timed step left for its caller: the framebuffer in HBM
+        dump_outputs(dump_dir, {"frame": device_frame(r.frame_device_ptr(), W, H)})
     px = W * H
     b_px = survey_bytes_per_px(prm)
     frame_gbs = b_px * px / (ms_per_step * 1e-3) / 1e9
-    k_gbs = PASS_BYTES[dom] * px / (iso[dom] * 1e-3) / 1e9
     _, last_kind, _ = r.traversal(gs)
     pmc = pmc_for(name, W, H)
     out = {
@@ -332,21 +365,36 @@ def run_single(name, W, H, steps, warmup, device, stream, cpu_threads, with_cpu,
                    "traversal": {0: "lockstep", 1: "lane"}.get(last_kind, str(last_kind)), "frames_in_flight": 3,
                    "scene_build_ms": round(float(gs.build_ms), 2), "wide_tree": gs.wide_tree_nodes()},
         "mrays_per_s": round(rays / dt / 1e6, 2), "rays_per_frame": rays // max(1, steps),
-        "pass_ms_one_frame_in_flight": {k: round(v, 4) for k, v in iso.items()},
-        "frame_ms_one_frame_in_flight": round(iso_total, 4),
         "roofline": {"bound": "hbm", "scope": "frame (all passes, frames in flight)", "bytes_per_px": b_px,
                      "achieved": round(frame_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(frame_gbs / HBM_PEAK_GBS, 5),
                      "traffic": pmc.get("frame_bytes") if pmc else None},
-        "kernel_roofline": {"bound": "hbm", "kernel": PASS_KERNEL[dom], "bytes_per_px": PASS_BYTES[dom],
-                            "kernel_ms": round(iso[dom], 4), "achieved": round(k_gbs, 2), "peak": HBM_PEAK_GBS,
-                            "unit": "GB/s", "frac": round(k_gbs / HBM_PEAK_GBS, 5),
-                            "kernel_ms_le_ms_per_step": bool(iso[dom] <= ms_per_step),
-                            "traffic": (pmc.get("kernels", {}).get(PASS_KERNEL[dom], {}) or {}).get("hbm_bytes_corrected")
-                            if pmc else None,
-                            "timing": f"HIP events on the frame's stream, {kn} frames with one frame in flight"},
     }
-    out["limiter"] = limiter_for(pmc, PASS_KERNEL[dom])
+    if full:
+        # kernel window: one frame in flight (run-ahead 0), HIP events around every pass on the frame's stream
+        r.set_run_ahead(0)
+        for f in range(2):
+            step(warmup + steps + f)
+        r.timing_totals(reset=True)
+        for f in range(kernel_frames):
+            step(warmup + steps + 2 + f)
+        ktot, kn = r.timing_totals(reset=True)
+        r.set_run_ahead(2)
+        iso = {k: float(getattr(ktot, k)) / max(1, kn) for k in PASS_BYTES}
+        iso_total = float(ktot.total_ms) / max(1, kn)
+        dom = max(iso, key=iso.get)
+        k_gbs = PASS_BYTES[dom] * px / (iso[dom] * 1e-3) / 1e9
+        out["pass_ms_one_frame_in_flight"] = {k: round(v, 4) for k, v in iso.items()}
+        out["frame_ms_one_frame_in_flight"] = round(iso_total, 4)
+        out["kernel_roofline"] = {
+            "bound": "hbm", "kernel": PASS_KERNEL[dom], "bytes_per_px": PASS_BYTES[dom],
+            "kernel_ms": round(iso[dom], 4), "achieved": round(k_gbs, 2), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac": round(k_gbs / HBM_PEAK_GBS, 5),
+            "kernel_ms_le_ms_per_step": bool(iso[dom] <= ms_per_step),
+            "traffic": (pmc.get("kernels", {}).get(PASS_KERNEL[dom], {}) or {}).get("hbm_bytes_corrected")
+            if pmc else None,
+            "timing": f"HIP events on the frame's stream, {kn} frames with one frame in flight"}
+        out["limiter"] = limiter_for(pmc, PASS_KERNEL[dom])
     if pmc and pmc.get("frame_valu"):
         v = float(pmc["frame_valu"])
         out["valu_issue"] = {"scope": "frame", "valu_per_frame": v, "achieved": round(v / (ms_per_step * 1e-3) / 1e9, 2),
@@ -594,12 +642,13 @@ def launch_ranks(argv, world: int, env=None, cmd=None, poll_s: float = 0.2) -> i
     return rc
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = parse(argv)
     verdict = check_world(args.gpus, os.environ)
     if verdict == "launch":
         # --gpus N > 1 without a launcher: start N ranks here, before this process touches the GPU
-        sys.exit(launch_ranks(sys.argv[1:], args.gpus))
+        sys.exit(launch_ranks(argv, args.gpus))
     if verdict is not None:
         print(f"bench.py: {verdict}", file=sys.stderr)
         sys.exit(2)
@@ -616,7 +665,7 @@ def main():
         torch.cuda.set_stream(torch.cuda.Stream(device=local))
         stream = torch.cuda.current_stream().cuda_stream
         head = run_single(args.scene, W, H, args.steps, args.warmup, local, stream, args.cpu_threads,
-                          not args.no_cpu_baseline)
+                          args.full and not args.no_cpu_baseline, full=args.full, dump_dir=args.dump_outputs)
         out = {"metric": METRIC, "value": head.pop("value"), "unit": "frames/s", "n_gpus": 1,
                "steps": args.steps, "warmup": args.warmup, "ms_per_step": head.pop("ms_per_step"),
                "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
@@ -624,7 +673,7 @@ def main():
         head["config"]["parallelism"] = "1 GPU"
         out.update(head)
         full = dict(out)
-        if not args.no_extras and args.scene == "C2" and (W, H) == (1920, 1080):
+        if args.full and not args.no_extras and args.scene == "C2" and (W, H) == (1920, 1080):
             extras = {}
             for name, steps, res in (("C3", 20, (W, H)), ("C5", C5_FRAMES, (W, H)), ("C2V", args.steps, (W, H)),
                                      ("C4_1gpu", 10, RES["C4"])):
@@ -646,20 +695,22 @@ def main():
                 extras["dropin_host_framebuffer"] = d
             full["configs"] = extras
             out["configs"] = {k: compact(v) for k, v in extras.items()}
-        full["host"] = host_cpu()
-        write_full(args.full_out, full)
+        if args.full:
+            full["host"] = host_cpu()
+            write_full(args.full_out, full)
+            out["full_record"] = os.path.relpath(args.full_out, ROOT)
         for k in ("pass_ms_one_frame_in_flight", "frame_ms_one_frame_in_flight", "frames_timed_by_events",
                   "reference_rays_per_frame", "rays_per_frame"):
             out.pop(k, None)
         for k in ("roofline", "kernel_roofline"):
-            out[k] = _compact_roofline(out.get(k))
+            if k in out:
+                out[k] = _compact_roofline(out[k])
         if out.get("cpu_baseline"):
             out["cpu_baseline"] = {k: out["cpu_baseline"][k] for k in ("value", "unit", "cores", "kind", "sample")}
         if out.get("limiter"):
             out["limiter"] = {k: out["limiter"][k] for k in ("kernel", "bound_by", "source") if k in out["limiter"]}
         if out.get("valu_issue"):
             out["valu_issue"] = {k: out["valu_issue"][k] for k in ("achieved", "peak", "unit", "frac") if k in out["valu_issue"]}
-        out["full_record"] = os.path.relpath(args.full_out, ROOT)
         print(json.dumps(out), flush=True)
         return
     run_multi(args, world, rank, local, W, H)
@@ -673,12 +724,16 @@ def run_multi(args, world, rank, local, W, H):
     RESTIR_MGPU=python (or the RESTIR_DIST_BACKEND=gloo rehearsal with ranks sharing a GPU) runs the Python
     orchestration (restir_amd/distributed.py) instead."""
     if os.environ.get("RESTIR_MGPU", "cabi") == "python" or os.environ.get("RESTIR_DIST_BACKEND") == "gloo":
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs is not available with the Python orchestration (RESTIR_MGPU=python)")
         return run_multi_python(args, world, rank, local, W, H)
     import torch
     import torch.distributed as dist
     dist.init_process_group("gloo")
     torch.cuda.set_device(local)
-    names = [args.scene] + [c for c in args.multi_configs.split(",") if c and c != args.scene]
+    names = [args.scene]
+    if args.full:
+        names += [c for c in args.multi_configs.split(",") if c and c != args.scene]
     lines = {}
     for name in names:
         w, h = RES.get(name, (W, H))
@@ -689,10 +744,11 @@ def run_multi(args, world, rank, local, W, H):
         if len(names) > 1:
             full["configs"] = {n: lines[n] for n in names[1:]}
             head["configs"] = {n: compact(lines[n]) for n in names[1:]}
-        full["host"] = host_cpu()
-        write_full(args.full_out, full)
         head["per_rank"] = compact(head)["per_rank"]
-        head["full_record"] = os.path.relpath(args.full_out, ROOT)
+        if args.full:
+            full["host"] = host_cpu()
+            write_full(args.full_out, full)
+            head["full_record"] = os.path.relpath(args.full_out, ROOT)
         print(json.dumps(head), flush=True)
     dist.barrier()
     dist.destroy_process_group()
@@ -735,6 +791,8 @@ def run_multi_config(args, name, world, rank, local, W, H):
     torch.cuda.synchronize()
     dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and name == args.scene:      # the gathered frame of the last timed step
+        dump_outputs(args.dump_outputs, {"frame": device_frame(m.frame_device_ptr(), W, H)})
     tot, n_timed = r.timing_totals()
     xs = m.stats()
     red = torch.tensor([dt, float(tot.rays), float(tot.reproj_outside)], dtype=torch.float64)

@@ -81,7 +81,7 @@ step_ab() {
   for rep in $(seq ${REPS:-2}); do
     for so in restir-embree_amd/_ab/*.so; do
       local n=$(basename $so .so)
-      RESTIR_LIB=$PWD/$so timeout -k 10 240 python bench.py --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-extras ${BENCH_ARGS} \
+      RESTIR_LIB=$PWD/$so timeout -k 10 240 python bench.py --full --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-extras ${BENCH_ARGS} \
         > gpurun_out/ab_$n.log 2>&1; local rc=$?
       [ $rc -ne 0 ] && { echo "$n rc=$rc"; tail -3 gpurun_out/ab_$n.log; return $rc; }
       python3 - "$n" gpurun_out/ab_$n.log <<'PY'
@@ -100,7 +100,7 @@ step_abenv() {
     IFS=';'; local sets=($ENVS); IFS="$IFS_OLD"
     for e in "${sets[@]}"; do
       local tag=$(echo "${e:-default}" | tr ' =/' '_-_' | cut -c1-80)
-      env $e timeout -k 10 240 python bench.py --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-extras ${BENCH_ARGS} \
+      env $e timeout -k 10 240 python bench.py --full --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-extras ${BENCH_ARGS} \
         > gpurun_out/abenv_$tag.log 2>&1; local rc=$?
       [ $rc -ne 0 ] && { echo "$tag rc=$rc"; tail -3 gpurun_out/abenv_$tag.log; return $rc; }
       python3 - "$tag" gpurun_out/abenv_$tag.log <<'PY'

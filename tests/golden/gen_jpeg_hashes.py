@@ -1,17 +1,20 @@
-"""Writes tests/golden/jpeg_reference_hashes.json: for every JPEG under /root/reference/template (the
-reference's textures, decoded there by FreeImage, pg/Texture.cpp:18-30), the shape and SHA-256 of the pixel
-array PIL's libjpeg-turbo decodes (default settings: islow IDCT, fancy upsampling).  The reference files are
-read as data, never executed; only the hashes are committed (tests/test_image_io.py compares rs_image_decode
-with them when /root/reference is present).  Run: python tests/golden/gen_jpeg_hashes.py"""
+"""Writes tests/golden/jpeg_reference_hashes.json: for every JPEG under the directory given on the command line
+(the `template` directory of a Tonz24/restir-embree checkout: the reference's textures, decoded there by
+FreeImage, pg/Texture.cpp:18-30), the shape and SHA-256 of the pixel array PIL's libjpeg-turbo decodes (default
+settings: islow IDCT, fancy upsampling).  The reference files are read as data, never executed; the hashes of all
+of them are committed, and six small textures themselves under tests/golden/jpeg/<same relative path>
+(tests/test_image_io.py compares rs_image_decode of those with their hashes).
+Run: python tests/golden/gen_jpeg_hashes.py <restir-embree>/template"""
 import glob
 import hashlib
 import json
 import os
+import sys
 
 import numpy as np
 from PIL import Image
 
-ROOT = "/root/reference/template"
+ROOT = sys.argv[1]
 out = {}
 for path in sorted(glob.glob(os.path.join(ROOT, "**", "*.jp*g"), recursive=True)):
     with Image.open(path) as im:

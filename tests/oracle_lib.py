@@ -5,6 +5,7 @@ leg as the checker / CPU baseline.  The product never imports this module.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import subprocess
@@ -34,6 +35,19 @@ def build():
     if (not os.path.exists(LIB_PATH)) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(p) for p in srcs):
         subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
     return LIB_PATH
+
+
+@contextlib.contextmanager
+def num_threads(n):
+    """The oracle on `n` OpenMP threads inside the block; afterwards the count from before is back (the setting
+    is the process's, and the full-size frames of later tests are rendered on every core it had)."""
+    L = lib()
+    prev = L.or_num_threads()
+    L.or_set_num_threads(n)
+    try:
+        yield
+    finally:
+        L.or_set_num_threads(prev)
 
 
 def lib():

@@ -96,7 +96,14 @@ def test_halo_rows_and_bands():
     assert halo_rows(P.metric_params(spatial_radius=24.9)) == 4
 
 
-def test_oracle_tiles_halo_margin_rebuild_bit_identical():
+@pytest.fixture
+def four_oracle_threads():
+    import oracle_lib as O
+    with O.num_threads(4):
+        yield
+
+
+def test_oracle_tiles_halo_margin_rebuild_bit_identical(four_oracle_threads):
     """Tile stages with a G-buffer margin of only the spatial halo under a moving camera (the miss pixels
     around the box have position (0,0,0), which projects into other bands): the temporal pass rebuilds the
     G elements beyond a tile's rows (counted: the path runs), so 4 in-process bands (halo copies between
@@ -104,7 +111,6 @@ def test_oracle_tiles_halo_margin_rebuild_bit_identical():
     import oracle_lib as O
     from restir_amd import params as P, scenes
     from restir_amd.distributed import band_rows, halo_rows
-    O.lib().or_set_num_threads(4)
     sc = scenes.cornell_many_lights(64)
     W, H, N = 96, 72, 4
     prm = P.c3_params(m_area=4)

@@ -42,10 +42,15 @@ def _harness():
     return L
 
 
+@pytest.fixture
+def four_oracle_threads():
+    with O.num_threads(4):
+        yield
+
+
 @pytest.mark.parametrize("n,which", [(2, "c1"), (3, "c3"), (4, "c2")])
-def test_native_orchestration_matches_full_frames(n, which):
+def test_native_orchestration_matches_full_frames(n, which, four_oracle_threads):
     L = _harness()
-    O.lib().or_set_num_threads(4)
     W, H = 64, 48
     if which == "c1":
         sc, prm = scenes.cornell_box(8), P.default_params(m_area=4, do_spatial=1, spatial_passes=2, do_temporal=1)

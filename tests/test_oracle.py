@@ -355,9 +355,7 @@ def _brute_closest_segment(sc, o, d, tf):
 
 
 # ---------------------------------------------------------------- oracle frame invariants
-def _render(sc, W, H, prm, frames=1, threads=None, cam=None):
-    if threads:
-        O.lib().or_set_num_threads(threads)
+def _render(sc, W, H, prm, frames=1, cam=None):
     os_ = O.OracleScene(sc)
     r = O.OracleRenderer(W, H)
     img = None
@@ -389,9 +387,10 @@ def test_oracle_deterministic_across_thread_counts(mis):
     sc = scenes.cornell_box(8)
     prm = P.default_params(m_area=4, do_spatial=1, spatial_neighbors=3, do_temporal=1, spatial_mis=mis)
     cam = lambda f: scenes.orbit_camera(sc.camera, f, 24, 0.2)
-    a, _ = _render(sc, 48, 40, prm, frames=2, threads=1, cam=cam)
-    b, _ = _render(sc, 48, 40, prm, frames=2, threads=8, cam=cam)
-    O.lib().or_set_num_threads(os.cpu_count() or 1)
+    with O.num_threads(1):
+        a, _ = _render(sc, 48, 40, prm, frames=2, cam=cam)
+    with O.num_threads(8):
+        b, _ = _render(sc, 48, 40, prm, frames=2, cam=cam)
     assert np.array_equal(a, b)
 
 
