@@ -250,6 +250,8 @@ struct rs_context {
     int sort_spatial = RS_SPLIT_AUTO;      // wave-sorted spatial pass, CONSTANT MIS, k <= 8 (RESTIR_SORT_SPATIAL=on|off;
                                            // AUTO: per-lane walks -- C3 2.21 -> 1.87 ms; lockstep C5 0.228 -> 0.250)
     int sort_temporal = RS_SPLIT_AUTO;     // wave-sorted temporal rays (RESTIR_SORT_TEMPORAL=off: per-ray walks)
+    bool light_lds = true;                 // the one-thread-per-pixel initial pass picks lights from an LDS copy of the
+                                           // tables when they fit (use_light_lds; RESTIR_LIGHT_LDS=off: global tables)
 };
 
 // --------------------------------------------------------------------------- helpers
@@ -427,6 +429,8 @@ extern "C" int rs_context_create(int hip_device, int width, int height, void* hi
         if (!std::strcmp(t, "on")) c->sort_spatial = RS_SPLIT_ON;
         else if (!std::strcmp(t, "off")) c->sort_spatial = RS_SPLIT_OFF;
     }
+    if (const char* t = std::getenv("RESTIR_LIGHT_LDS"))       // auto (default) | off: light tables from global memory
+        c->light_lds = std::strcmp(t, "off") != 0;
     if (const char* t = std::getenv("RESTIR_TILE_ORDER"))      // cost (default) | off (row-major)
         c->order_on = std::strcmp(t, "off") != 0;
     if (const char* t = std::getenv("RESTIR_READBACK"))        // sdma (default) | kernel
@@ -1484,6 +1488,13 @@ static bool want_sorted(const rs_context* c, const rs_frame_params* P, const rs_
     if (P->m_area <= 0 || s->n_emis >= (1u << 21) || c->sort_mode == RS_SPLIT_OFF) return false;
     return c->sort_mode == RS_SPLIT_ON || c->trav == TRAV_LANE;
 }
+// the one-thread-per-pixel initial pass with the light tables in LDS (rs_passes.h LIGHT_LDS): when the scene's CDF
+// fits the kernel's static arrays and area candidates are drawn at all; larger scenes keep the global tables.
+// Lockstep walks only: the per-lane kernel is budgeted for 6 waves per SIMD, which 30 KB of LDS per workgroup
+// does not leave (and per-lane scenes take the sorted pass, whose LDS is full)
+static bool use_light_lds(const rs_context* c, const rs_frame_params* P, const rs_scene* s) {
+    return c->light_lds && c->trav == TRAV_LOCKSTEP && P->m_area > 0 && s->n_emis > 0 && s->n_emis <= (uint32_t)kLightLdsMax;
+}
 static dim3 grid_split(int W, int ya, int yb) { return dim3((W + 7) / 8, (yb - ya + 7) / 8); }
 // the initial pass runs candidate-split when asked, or (AUTO) when one thread per pixel would give the
 // launch too few rounds of the device's resident waves (a rank's band of a multi-GPU frame) and
@@ -1727,6 +1738,14 @@ extern "C" int rs_tile_begin(rs_context* c, const rs_scene* s, const rs_camera* 
             LAUNCH_TRAV(c, k_gbuffer_initial_sorted, gg, S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, c->shade_fused ? 1 : 0,
                         count_slot(c, gg));
         }
+    } else if (use_light_lds(c, P, s)) {
+        const CountSlot cs = count_slot(c, gg);
+        if (c->twide)
+            k_gbuffer_initial<TRAV_LOCKSTEP | TRAV_WIDE | LIGHT_LDS><<<gg, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb,
+                                                                                 c->shade_fused ? 1 : 0, cs);
+        else
+            k_gbuffer_initial<TRAV_LOCKSTEP | LIGHT_LDS><<<gg, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb,
+                                                                     c->shade_fused ? 1 : 0, cs);
     } else {
         LAUNCH_TRAV(c, k_gbuffer_initial, gg, S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, c->shade_fused ? 1 : 0,
                     count_slot(c, gg));

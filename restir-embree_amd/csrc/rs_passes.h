@@ -325,23 +325,94 @@ __device__ __forceinline__ GElem gbuffer_fill(const DevScene& S, const FrameCons
 // TriangleCDF::getTriangle's index (pg/TriangleCDF.cpp:36-54): std::lower_bound(cdf2, ksi), narrowed
 // by the guide table: ksi*kCdfGuide is exact (ksi = k*2^-24), and lower_bound(j/G) <= lower_bound(ksi)
 // <= lower_bound((j+1)/G) for j = floor(ksi*G)
-__device__ __forceinline__ uint32_t light_index(const DevScene& S, float ksi) {
+// The search reads its two tables through a source L: the scene's arrays in global memory (LightGlobal), or
+// a workgroup's copy of them in LDS (LightLds, below).  Both hold the same values and the search makes the
+// same comparisons, so the index is the same bit for bit.
+struct LightGlobal {
+    const float* cdf_g;
+    const int* guide_g;
+    __device__ __forceinline__ explicit LightGlobal(const DevScene& S) : cdf_g(S.cdf), guide_g(S.cdf_guide) {}
+    __device__ __forceinline__ float cdf(uint32_t i) const { return cdf_g[i]; }
+    __device__ __forceinline__ uint32_t guide(uint32_t j) const { return (uint32_t)guide_g[j]; }
+};
+template <class LT>
+__device__ __forceinline__ uint32_t light_index(const LT& L, uint32_t n_emis, float ksi) {
     uint32_t j = (uint32_t)(ksi * (float)kCdfGuide);
-    uint32_t lo = (uint32_t)S.cdf_guide[j], n = (uint32_t)S.cdf_guide[j + 1] + 1u - lo;
-    if (lo + n > S.n_emis) n = S.n_emis - lo;
+    uint32_t lo = L.guide(j), n = L.guide(j + 1) + 1u - lo;
+    if (lo + n > n_emis) n = n_emis - lo;
     while (n > 0) {
         uint32_t h = n >> 1;
-        if (S.cdf[lo + h] < ksi) { lo = lo + h + 1; n = n - h - 1; } else n = h;
+        if (L.cdf(lo + h) < ksi) { lo = lo + h + 1; n = n - h - 1; } else n = h;
     }
-    return lo < S.n_emis ? lo : S.n_emis - 1;
+    return lo < n_emis ? lo : n_emis - 1;
 }
+__device__ __forceinline__ uint32_t light_index(const DevScene& S, float ksi) {
+    return light_index(LightGlobal(S), S.n_emis, ksi);
+}
+
+// The light tables of a small scene in LDS (k_gbuffer_initial<T | LIGHT_LDS>): the one-thread-per-pixel initial
+// pass picks a light per area candidate -- the guide pair, then ~1 dependent CDF gather per search step: 4-byte
+// loads whose 64 lanes land on tens of cache lines, a quarter of the C2 kernel's vector loads.
+// Up to kLightLdsMax emissive triangles the CDF (8 KB) and the guide (as uint16_t, 2 KB) fit beside the
+// ShadeFrame slots (20 KB) at the kernel's 5 workgroups per CU: 30.0 KB x 5 of the CU's 160 KiB.
+constexpr int kLightLdsMax = 2048;
+// guide entries are CDF indices <= n_emis <= kLightLdsMax (the launch rule, restir_capi.hip use_light_lds)
+static_assert(kLightLdsMax <= 65535, "the LDS guide holds CDF indices as uint16_t");
+static_assert(kLightLdsMax % 4 == 0 && kLightLdsMax / 4 == 2 * 256 && kCdfGuide == 4 * 256,
+              "LightFill: a 256-thread workgroup moves the CDF as 2 and the guide as 1 16-B load per thread");
+constexpr int LIGHT_LDS = 8;              // kernel template bit (beside Trav's): the light tables from LDS
+struct LightLds {
+    const float* cdf_l;                   // __shared__ float[kLightLdsMax]
+    const uint16_t* guide_l;              // __shared__ uint16_t[kCdfGuide + 1] (padded to 8 B)
+    __device__ __forceinline__ float cdf(uint32_t i) const { return cdf_l[i]; }
+    __device__ __forceinline__ uint32_t guide(uint32_t j) const { return (uint32_t)guide_l[j]; }
+};
+// A workgroup's copy: issue() starts the loads (coalesced, 16 B per lane), commit() writes LDS -- the caller puts
+// the primary-ray walk between them and a __syncthreads() after.  CDF entries at and beyond n_emis are never read
+// from global memory (their LDS words are padded with 1; light_index clamps its range to n_emis, so it does not
+// read them either); the guide always has its kCdfGuide + 1 entries.
+struct LightFill {
+    float4 c[2];
+    int4 g;
+    int g_end;
+    __device__ __forceinline__ static float4 cdf4(const float* cdf, uint32_t i, uint32_t n) {
+        if (4u * i + 4u <= n) return reinterpret_cast<const float4*>(cdf)[i];
+        float4 v = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+        if (4u * i < n) v.x = cdf[4u * i];
+        if (4u * i + 1u < n) v.y = cdf[4u * i + 1u];
+        if (4u * i + 2u < n) v.z = cdf[4u * i + 2u];
+        return v;
+    }
+    __device__ __forceinline__ void issue(const DevScene& S, uint32_t t) {
+        const uint32_t n = S.n_emis < (uint32_t)kLightLdsMax ? S.n_emis : (uint32_t)kLightLdsMax;
+        c[0] = cdf4(S.cdf, t, n);
+        c[1] = cdf4(S.cdf, t + 256u, n);
+        g = reinterpret_cast<const int4*>(S.cdf_guide)[t];
+        g_end = t == 0 ? S.cdf_guide[kCdfGuide] : 0;
+    }
+    // cdf_l: float[kLightLdsMax], 16-B aligned; guide_l: uint16_t[kCdfGuide + 4], 8-B aligned.  The arrays are read
+    // as what they are declared; only these vector stores go through a cast.  Four guide entries are packed into
+    // one 8-B store, entry 4t in the low half of the first word: gfx950 is little-endian.
+    __device__ __forceinline__ void commit(float* cdf_l, uint16_t* guide_l, uint32_t t) const {
+        float4* c4 = reinterpret_cast<float4*>(cdf_l);
+        uint2* g2 = reinterpret_cast<uint2*>(guide_l);
+        c4[t] = c[0];
+        c4[t + 256u] = c[1];
+        g2[t] = make_uint2((uint32_t)g.x | ((uint32_t)g.y << 16), (uint32_t)g.z | ((uint32_t)g.w << 16));
+        if (t == 0) guide_l[kCdfGuide] = (uint16_t)g_end;
+    }
+};
 
 // the emissive-triangle pick of candidate c alone (its first RNG slot): the CDF search is a chain of
 // dependent loads, so the initial pass issues the next batch's picks before the current batch's walk
-__device__ __forceinline__ uint32_t area_pick(const DevScene& S, const Rng& rng, int c) {
+template <class LT>
+__device__ __forceinline__ uint32_t area_pick(const LT& L, const DevScene& S, const Rng& rng, int c) {
     Rng q = rng;
     q.n = cand_slot(c);
-    return light_index(S, q.range(0.0f, 1.0f));
+    return light_index(L, S.n_emis, q.range(0.0f, 1.0f));
+}
+__device__ __forceinline__ uint32_t area_pick(const DevScene& S, const Rng& rng, int c) {
+    return area_pick(LightGlobal(S), S, rng, c);
 }
 // An emissive triangle's record, 8 float4 (one 128-B line):
 //   e0 (p0, pdf_area)  e1 (p1, n0.x)  e2 (p2, n0.y)  e3 (le, n0.z)
@@ -389,9 +460,10 @@ __device__ __forceinline__ Sample area_sample_at(const DevScene& S, const FrameC
     W_out = 1.0f / pdf_area;
     return Sample{pt, nn, E.le};
 }
-__device__ __forceinline__ Sample area_sample(const DevScene& S, const FrameConst& F, vec3 pos, const ShadeFrame& sf,
-                                              Rng& rng, float& W_out, float& mis_out) {
-    const uint32_t idx = light_index(S, rng.range(0.0f, 1.0f));
+template <class LT>
+__device__ __forceinline__ Sample area_sample(const LT& L, const DevScene& S, const FrameConst& F, vec3 pos,
+                                              const ShadeFrame& sf, Rng& rng, float& W_out, float& mis_out) {
+    const uint32_t idx = light_index(L, S.n_emis, rng.range(0.0f, 1.0f));
     return area_sample_at(S, F, pos, sf, rng, idx, W_out, mis_out);
 }
 
@@ -483,21 +555,27 @@ __device__ __forceinline__ void area_batch(const DevScene& S, const FrameConst& 
 #pragma unroll
     for (int k = 0; k < kB; ++k) w_out[k] = (okb[k] && !(act[k] && occ[k])) ? wu[k] : wo[k];   // evaluate_f_post
 }
-// the selected area candidate's sample and (unoccluded) f, re-drawn from its RNG slots
-__device__ __forceinline__ Sample area_redraw(const DevScene& S, const FrameConst& F, vec3 pos, const ShadeFrame& sf,
-                                             Rng& rng, int c, bool tv, vec3& f) {
+// the selected area candidate's sample and (unoccluded) f, re-drawn from its RNG slots (the pick through the
+// same table source L as the first draw's)
+template <class LT>
+__device__ __forceinline__ Sample area_redraw(const LT& L, const DevScene& S, const FrameConst& F, vec3 pos,
+                                             const ShadeFrame& sf, Rng& rng, int c, bool tv, vec3& f) {
     float Wc, mis;
     rng.n = cand_slot(c);
-    const Sample s = area_sample(S, F, pos, sf, rng, Wc, mis);
+    const Sample s = area_sample(L, S, F, pos, sf, rng, Wc, mis);
     f = evaluate_f_pre(F, s, pos, false, sf, tv, true).L;
     return s;
+}
+__device__ __forceinline__ Sample area_redraw(const DevScene& S, const FrameConst& F, vec3 pos, const ShadeFrame& sf,
+                                             Rng& rng, int c, bool tv, vec3& f) {
+    return area_redraw(LightGlobal(S), S, F, pos, sf, rng, c, tv, f);
 }
 
 // initialRenderPass (pg/ReSTIRIntegrator.cpp:236-298) for the lanes with `in_pass`.  f_sel returns the
 // selected candidate's f (for the fused shade); the final p-hat (:289) equals the selected candidate's
 // p-hat (same arguments), so it is not re-evaluated.
-template <int T>
-__device__ __forceinline__ Res initial_ris(const DevScene& S, const FrameConst& F, vec3 pos, bool emissive,
+template <int T, class LT>
+__device__ __forceinline__ Res initial_ris(const LT& L, const DevScene& S, const FrameConst& F, vec3 pos, bool emissive,
                                            FrameSlot fs, uint32_t pix, bool in_pass, vec3& f_sel, uint32_t& rays) {
     f_sel = mk(0, 0, 0);
     Res r = res_empty();
@@ -514,12 +592,12 @@ __device__ __forceinline__ Res initial_ris(const DevScene& S, const FrameConst& 
         int sel = -1;
         uint32_t pick[kB];
 #pragma unroll
-        for (int k = 0; k < kB; ++k) pick[k] = area_pick(S, rng, k);
+        for (int k = 0; k < kB; ++k) pick[k] = area_pick(L, S, rng, k);
         for (int c0 = 0; c0 < F.m_area; c0 += kB) {
             float w[kB];
             uint32_t next[kB];
 #pragma unroll
-            for (int k = 0; k < kB; ++k) next[k] = area_pick(S, rng, c0 + kB + k);   // in flight during the walk
+            for (int k = 0; k < kB; ++k) next[k] = area_pick(L, S, rng, c0 + kB + k);   // in flight during the walk
             area_batch<T, kB>(S, F, pos, fs.load(), rng, c0, F.m_area, alive, tv, pick, w, rays);
 #pragma unroll
             for (int k = 0; k < kB; ++k) pick[k] = next[k];
@@ -532,7 +610,7 @@ __device__ __forceinline__ Res initial_ris(const DevScene& S, const FrameConst& 
             }
         }
         if (sel >= 0) {
-            const Sample s = area_redraw(S, F, pos, fs.load(), rng, sel, tv, f_sel);
+            const Sample s = area_redraw(L, S, F, pos, fs.load(), rng, sel, tv, f_sel);
             best_phat = length(f_sel);
             r.p = s.p; r.n = s.n; r.li = s.li;
         }
@@ -623,27 +701,29 @@ __device__ __forceinline__ void count_store(CountSlot C, uint32_t rays, uint32_t
         C.part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * (blockDim.x >> 6) + (threadIdx.x >> 6)] = make_uint2(r, p);
 }
 
-// G-buffer + initialRenderPass of one pixel (the body of k_gbuffer_initial)
-template <int T>
-__device__ __forceinline__ void gbuffer_initial_px(const DevScene& S, const FrameConst& F, const GBuf& G, const ResBuf& Rw,
-                                                   float* fb, int fuse_shade, const FrameSlot& fs, int x, int y, bool in,
-                                                   uint32_t& rays) {
+// G-buffer + initialRenderPass of one pixel (the body of k_gbuffer_initial); T's walk bits only
+template <int T, class LT>
+__device__ __forceinline__ void initial_px(const LT& L, const DevScene& S, const FrameConst& F, const GElem& g,
+                                           const ResBuf& Rw, float* fb, int fuse_shade, const FrameSlot& fs, int x, int y,
+                                           bool in, uint32_t& rays) {
     const size_t p = (size_t)y * F.W + x;
-    GElem g = gbuffer_fill<T>(S, F, x, y, in);
-    if (in) G.store(p, g);
-    fs.store(make_frame(g, F.cam.pos));
     const bool ris = in && y >= F.y0 && y < F.y1;
     vec3 f;
-    Res r = initial_ris<T>(S, F, g.pos, any_pos(g.le), fs, (uint32_t)p, ris, f, rays);
+    Res r = initial_ris<T>(L, S, F, g.pos, any_pos(g.le), fs, (uint32_t)p, ris, f, rays);
     if (ris) {
         Rw.store(p, r);
         if (fuse_shade) store_rgb(fb, p, shade_px(r, f, g.le));
     }
 }
+// T | LIGHT_LDS: the light tables from a workgroup copy in LDS (LightLds; launched for 0 < n_emis <= kLightLdsMax).
+// Every thread of the workgroup -- lanes clamped into the image included -- takes part in the copy and reaches the
+// barrier, which stands in front of initial_ris's wave-uniform exit; the copy's loads are in flight during the
+// primary-ray walk.
 template <int T>
 __global__ void __launch_bounds__(256, RS_WAVES(T, RS_INITIAL_WAVES, RS_INITIAL_WAVES_LANE)) k_gbuffer_initial(DevScene S, FrameConst F, GBuf G,
                                                                             ResBuf Rw, float* fb, int fuse_shade,
                                                                             CountSlot C) {
+    constexpr int TT = T & ~LIGHT_LDS;
     const uint64_t t0 = wave_clock();
     if ((blockIdx.x | blockIdx.y | threadIdx.x) == 0) *C.outside = 0ull;   // this frame's counter (rs_tile_begin)
     int x, y;
@@ -651,7 +731,21 @@ __global__ void __launch_bounds__(256, RS_WAVES(T, RS_INITIAL_WAVES, RS_INITIAL_
     const bool in = pixel_of(F, F.gy0, F.gy1, x, y);
     __shared__ float4 frame_lds[5 * 256];
     const FrameSlot fs{frame_lds, (int)threadIdx.x, 256};
-    gbuffer_initial_px<T>(S, F, G, Rw, fb, fuse_shade, fs, x, y, in, rays);
+    LightFill fill;
+    if constexpr ((T & LIGHT_LDS) != 0) fill.issue(S, threadIdx.x);
+    const GElem g = gbuffer_fill<TT>(S, F, x, y, in);
+    if (in) G.store((size_t)y * F.W + x, g);
+    fs.store(make_frame(g, F.cam.pos));
+    if constexpr ((T & LIGHT_LDS) != 0) {
+        __shared__ alignas(16) float cdf_lds[kLightLdsMax];
+        __shared__ alignas(8) uint16_t guide_lds[kCdfGuide + 4];     // kCdfGuide + 1 entries, padded to 8 B
+        fill.commit(cdf_lds, guide_lds, threadIdx.x);
+        __syncthreads();
+        const LightLds L{cdf_lds, guide_lds};
+        initial_px<TT>(L, S, F, g, Rw, fb, fuse_shade, fs, x, y, in, rays);
+    } else {
+        initial_px<TT>(LightGlobal(S), S, F, g, Rw, fb, fuse_shade, fs, x, y, in, rays);
+    }
     count_rays(C, rays + (in ? 1u : 0u), in ? 1u : 0u, t0, y);
 }
 // ---------------------------------------------------------------- wave-sorted initial pass (per-lane wide walks)

@@ -60,7 +60,8 @@ step_pmc() {
     [ -n "$PMC_ENV" ] && export $PMC_ENV
     for cfg in ${CFGS:-C2 C3}; do
       local trav=lockstep; [ $cfg = C3 ] && trav=lane
-      for C in FETCH_SIZE WRITE_SIZE "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY" "$TA"; do
+      for C in FETCH_SIZE WRITE_SIZE "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY" "$TA" \
+               "SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS"; do
         local D=${C%% *}
         RESTIR_RUNAHEAD=0 RESTIR_TRAVERSAL=$trav timeout -s KILL 240 rocprofv3 --pmc $C --output-format csv \
           -d "$R/gpurun_out/pmc_${cfg}${PMC_TAG}_$D" -o run -- \

@@ -81,6 +81,18 @@ if os.path.exists(ta_csv):   # vector-memory pipeline group: per-launch means, a
             "note": "busy fractions: TA_TA_BUSY / TD_TD_BUSY / 256 CUs / (GRBM_GUI_ACTIVE / 8 XCDs); VALU issue: "
                     "SQ_INSTS_VALU / (1024 SIMDs x active cycles / 2 cycles per wave64 instruction); cache accesses per "
                     "vector load instruction = TCP_TOTAL_CACHE_ACCESSES / SQ_INSTS_VMEM_RD"}
+lds_csv = os.path.join(src, f"pmc_{cfg}{TAG}_SQ_INSTS_LDS", "run_counter_collection.csv")
+if os.path.exists(lds_csv):   # LDS group: per-launch means (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE are cycles)
+    lds = collections.defaultdict(lambda: collections.defaultdict(list))
+    with open(lds_csv) as f:
+        for row in csv.DictReader(f):
+            lds[kname(row)][row["Counter_Name"]].append(float(row["Counter_Value"]))
+    for k, d in lds.items():
+        if k in res["kernels"]:
+            m = {c: sum(v) / len(v) for c, v in d.items()}
+            res["kernels"][k]["lds"] = {c: round(v, 1) for c, v in m.items()}
+            res["kernels"][k]["lds"]["bank_conflict_over_idx_active"] = round(
+                m.get("SQ_LDS_BANK_CONFLICT", 0.0) / max(1.0, m.get("SQ_LDS_IDX_ACTIVE", 0.0)), 4)
 # one frame = one launch of each pass kernel present
 res["frame_bytes"] = sum(v["hbm_bytes_corrected"] for v in res["kernels"].values())
 res["frame_valu"] = sum(v.get("sq", {}).get("SQ_INSTS_VALU", 0.0) for v in res["kernels"].values()) or None

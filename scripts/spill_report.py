@@ -121,6 +121,16 @@ def main():
             hist[sz] = hist.get(sz, 0) + 1
         print(f"{name[:64]}: {len(ops)} scratch ops, {len(inner)} in loops (innermost loop length: ops "
               f"{dict(sorted(hist.items()))})")
+        # the code object's metadata for the kernel: static LDS, registers, and its vector-memory loads
+        md = s.find(f".amdhsa_kernel {name}\n")
+        if md >= 0:
+            d = s[md:s.find(".end_amdhsa_kernel", md)]
+            get = lambda k: (re.search(rf"\.amdhsa_{k} (\S+)", d) or [None, "?"])[1]
+            vm = sum(1 for l in body if re.match(r"\s*(global|flat|buffer)_load", l))
+            ds = sum(1 for l in body if re.match(r"\s*ds_read", l))
+            print(f"    group_segment_fixed_size {get('group_segment_fixed_size')}, next_free_vgpr {get('next_free_vgpr')}, "
+                  f"accum_offset {get('accum_offset')}, private_segment_fixed_size {get('private_segment_fixed_size')}; "
+                  f"{vm} vector-memory loads, {ds} LDS reads")
 
 
 if __name__ == "__main__":
