@@ -17,6 +17,7 @@
 // The context picks the faster kind per scene by timing (restir_capi.hip pick_traversal).
 #pragma once
 #include "rs_device.h"
+#include "rs_lockstep.h"
 
 namespace rs {
 
@@ -474,7 +475,9 @@ __device__ __forceinline__ Hit closest_lane(const DevScene& S, bool active, vec3
 // The skip-pointer order is a global order and every ray only moves forward through it, so a wave
 // can walk the node array together: each step it takes m = min over lanes of their next node, loads
 // node m ONCE with scalar loads (uniform address, no 64-address gather), and only the lanes whose
-// next node is m test it.  The number of steps is the size of the union of the lanes' paths -- for
+// next node is m test it.  The next m follows from the skip order (rs_lockstep.h: m + 1 or skip(m)); a
+// cross-lane minimum is taken only after a leaf step on which every ray on the node ended.  The number
+// of steps is the size of the union of the lanes' paths -- for
 // a wave's shadow rays from one 8x8 tile this is ~ the longest single path (scripts/bvh_analysis.py:
 // union 30.4 vs longest 28.9 nodes on C2) -- while per-step memory traffic drops from up to 64 cache
 // lines to one.  For incoherent rays the union approaches the sum of the paths (C3: 4x slower than
@@ -514,12 +517,35 @@ __device__ __forceinline__ uint32_t lane_min(const uint32_t* cur) {
     for (int k = 1; k < K; ++k) lm = cur[k] < lm ? cur[k] : lm;
     return lm;
 }
-// Next step's node after a lockstep step at m.  Every cursor is > m afterwards (lanes on m moved to
-// m + 1, skip(m) > m or done; the others were already > m), so if any lane descended to m + 1 that is
-// the minimum -- the cross-lane reduction is only needed when no lane descended.
-__device__ __forceinline__ uint32_t next_min(bool full, bool descended, uint32_t m, uint32_t lane_min_v) {
-    if (__ballot(descended) != 0) return m + 1;
-    return wave_min(full, lane_min_v);
+// The node after a lockstep step at m (rs_lockstep.h lockstep_next: m + 1, skip(m), or -- only when every ray on a
+// leaf ended there -- the minimum over the wave of each lane's smallest cursor `lane_min_v`).  EXEC is the walk's
+// own mask here (the callers branch on wave-uniform values only), so "all 64 lanes" is tested on this rare path.
+__device__ __forceinline__ uint32_t lockstep_step(bool leaf, bool descended, bool survivor, uint32_t m, uint32_t skip,
+                                                 uint32_t lane_min_v) {
+    const uint32_t next = lockstep_next(leaf, __ballot(descended) != 0, __ballot(survivor) != 0, m, skip);
+    if (!leaf || next != kLockstepReduce) return next;        // leaf is a constant at every call site
+    return wave_min(__ballot(1) == ~0ull, lane_min_v);
+}
+
+// The any-hit walks' box test.  fmaxf / fminf quiet a signalling NaN operand first, and the compiler cannot see
+// across the loop that tnear and tfar never change: box_test costs one v_max_f32 x, x for each of them at every
+// step.  A walk canonicalises both once (walk_bound) and clamps with the instructions themselves here -- the ones
+// the compiler selects for box_test's fmaxf / fminf chains, in the same order, so every value is box_test's.
+__device__ __forceinline__ float walk_bound(float x) { return __builtin_canonicalizef(x); }
+__device__ __forceinline__ bool box_test_walk(float4 a, float4 b, vec3 o, vec3 inv, float tnear_c, float tfar_c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    float tx0 = (a.x - o.x) * inv.x, tx1 = (b.x - o.x) * inv.x;
+    float ty0 = (a.y - o.y) * inv.y, ty1 = (b.y - o.y) * inv.y;
+    float tz0 = (a.z - o.z) * inv.z, tz1 = (b.z - o.z) * inv.z;
+    float t0, t1;
+    asm("v_max_f32 %0, %1, %2" : "=v"(t0) : "v"(tnear_c), "v"(fminf(tx0, tx1)));
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(t0) : "v"(t0), "v"(fminf(ty0, ty1)), "v"(fminf(tz0, tz1)));
+    asm("v_min_f32 %0, %1, %2" : "=v"(t1) : "v"(tfar_c), "v"(fmaxf(tx0, tx1)));
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(t1) : "v"(t1), "v"(fmaxf(ty0, ty1)), "v"(fmaxf(tz0, tz1)));
+    return t0 * (1.0f - 4.0f * FLT_EPSILON) <= t1 * (1.0f + 4.0f * FLT_EPSILON);
+#else
+    return box_test(a, b, o, inv, tnear_c, tfar_c);   // host pass only type-checks device code
+#endif
 }
 
 // K any-hit rays per lane sharing one origin (a pixel's shadow rays to K light samples), one lockstep
@@ -528,13 +554,17 @@ __device__ __forceinline__ uint32_t next_min(bool full, bool descended, uint32_t
 template <int K>
 __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const bool* active, vec3 o, const vec3* d,
                                                     float tnear, const float* tfar, bool* occ) {
-    const bool full = __ballot(1) == ~0ull;
     vec3 inv[K];
     uint32_t cur[K];
+    float tfar_c[K];
+    const float tnear_c = walk_bound(tnear);
+    bool live = false;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         inv[k] = mk(1.0f / d[k].x, 1.0f / d[k].y, 1.0f / d[k].z);
-        cur[k] = active[k] ? 0u : 0xffffffffu;
+        cur[k] = active[k] ? 0u : kLockstepDone;
+        tfar_c[k] = walk_bound(tfar[k]);
+        live |= active[k];
         occ[k] = false;
     }
     const uint32_t n = S.n_nodes;
@@ -543,7 +573,7 @@ __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const boo
     // s_andn2/s_and/s_or at every join -- that bookkeeping made SALU the busiest unit.  Only
     // wave-uniform branches remain (leaf or not, ballot tests).
     uint32_t occb = 0u;
-    uint32_t m = wave_min(full, lane_min<K>(cur));
+    uint32_t m = lockstep_first(__ballot(live) != 0);
     while (m < n) {
         float4 a, b;
         node_load(S.nodes, m, a, b);
@@ -551,7 +581,8 @@ __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const boo
         const int leaf = __float_as_int(b.w);
         uint32_t hbb = 0u;
 #pragma unroll
-        for (int k = 0; k < K; ++k) hbb |= (cur[k] == m && box_test(a, b, o, inv[k], tnear, tfar[k])) ? (1u << k) : 0u;
+        for (int k = 0; k < K; ++k)
+            hbb |= (cur[k] == m && box_test_walk(a, b, o, inv[k], tnear_c, tfar_c[k])) ? (1u << k) : 0u;
         if (leaf >= 0) {                                      // wave-uniform
             const int first = leaf >> 3, cnt = (leaf & 7) + 1;
             for (int j = 0; j < cnt; ++j) {
@@ -568,14 +599,18 @@ __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const boo
                     }
                 }
             }
+            bool survivor = false;                            // a ray on m that goes on to skip(m)
 #pragma unroll
-            for (int k = 0; k < K; ++k)
-                cur[k] = cur[k] == m ? (((hbb & occb) >> k) & 1u ? 0xffffffffu : skip) : cur[k];
-            m = wave_min(full, lane_min<K>(cur));
+            for (int k = 0; k < K; ++k) {
+                const bool on = cur[k] == m, ended = ((hbb & occb) >> k) & 1u;
+                cur[k] = on ? (ended ? kLockstepDone : skip) : cur[k];
+                survivor |= on & !ended;
+            }
+            m = lockstep_step(true, false, survivor, m, skip, lane_min<K>(cur));
         } else {
 #pragma unroll
             for (int k = 0; k < K; ++k) cur[k] = cur[k] == m ? ((hbb >> k) & 1u ? m + 1 : skip) : cur[k];
-            m = next_min(full, hbb != 0u, m, lane_min<K>(cur));
+            m = lockstep_step(false, hbb != 0u, false, m, skip, 0u);
         }
     }
 #pragma unroll
@@ -583,19 +618,19 @@ __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const boo
 }
 // one any-hit ray per lane (the K = 1 walk, written out: the leaf loop exits per lane)
 __device__ __forceinline__ bool occluded_wave(const DevScene& S, bool active, vec3 o, vec3 d, float tnear, float tfar) {
-    const bool full = __ballot(1) == ~0ull;
     vec3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    const float tnear_c = walk_bound(tnear), tfar_c = walk_bound(tfar);
     const uint32_t n = S.n_nodes;
-    uint32_t i = active ? 0u : 0xffffffffu;
+    uint32_t i = active ? 0u : kLockstepDone;
     uint32_t occ = 0u;                 // integer, not a bool: see occluded_wave_multi
-    uint32_t m = wave_min(full, i);
+    uint32_t m = lockstep_first(__ballot(active) != 0);
     while (m < n) {
         float4 a, b;
         node_load(S.nodes, m, a, b);
         const uint32_t skip = (uint32_t)__float_as_int(a.w);
         const int leaf = __float_as_int(b.w);
         const bool at = i == m;
-        const bool hb = at && box_test(a, b, o, inv, tnear, tfar);
+        const bool hb = at && box_test_walk(a, b, o, inv, tnear_c, tfar_c);
         if (leaf >= 0) {                                      // wave-uniform
             const int first = leaf >> 3, cnt = (leaf & 7) + 1;
             for (int k = 0; k < cnt; ++k) {
@@ -607,23 +642,24 @@ __device__ __forceinline__ bool occluded_wave(const DevScene& S, bool active, ve
                                              tnear, tfar, t, u, v);
                 occ = (want && hit) ? 1u : occ;
             }
-            i = at ? ((hb && occ) ? 0xffffffffu : skip) : i;
-            m = wave_min(full, i);
+            const bool ended = hb && occ;
+            i = at ? (ended ? kLockstepDone : skip) : i;
+            m = lockstep_step(true, false, at && !ended, m, skip, i);
         } else {
             i = at ? (hb ? m + 1 : skip) : i;
-            m = next_min(full, hb, m, i);
+            m = lockstep_step(false, hb, false, m, skip, 0u);
         }
     }
     return occ != 0u;
 }
+// one closest-hit ray per lane: no ray ends at a leaf, so the successor is always m + 1 or skip(m)
 __device__ __forceinline__ Hit closest_wave(const DevScene& S, bool active, vec3 o, vec3 d, float tnear, float tfar) {
-    const bool full = __ballot(1) == ~0ull;
     vec3 inv = mk(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     const MarginO mo = margin_origins(S, o);
     Hit h; h.t = tfar; h.u = 0; h.v = 0; h.prim = -1;
     const uint32_t n = S.n_nodes;
-    uint32_t i = active ? 0u : 0xffffffffu;
-    uint32_t m = wave_min(full, i);
+    uint32_t i = active ? 0u : kLockstepDone;
+    uint32_t m = lockstep_first(__ballot(active) != 0);
     while (m < n) {
         float4 a, b;
         node_load(S.nodes, m, a, b);
@@ -647,10 +683,10 @@ __device__ __forceinline__ Hit closest_wave(const DevScene& S, bool active, vec3
                 }
             }
             i = at ? skip : i;
-            m = wave_min(full, i);
+            m = lockstep_next(true, false, true, m, skip);    // the ray(s) on m go on
         } else {
             i = at ? (hb ? m + 1 : skip) : i;
-            m = next_min(full, hb, m, i);
+            m = lockstep_next(false, __ballot(hb) != 0, false, m, skip);
         }
     }
     return h;

@@ -983,6 +983,12 @@ int main(int argc, char** argv) {
                 for (size_t i = 0; i < order.size(); ++i) erank[order[i].second] = (uint32_t)((i << RB) / order.size());
             }
             double st[4] = {0, 0, 0, 0}, ds[4] = {0, 0, 0, 0}, bu[4] = {0, 0, 0, 0}, wu[4] = {0, 0, 0, 0};
+            // STEP_CLASSES: the binary lockstep walk of each candidate pair (the kernel's occluded_wave_multi<2>: lane =
+            // pixel, rays c and c + 1), its steps classified by what decides the next node (rs_lockstep.h): some ray
+            // descended / interior node nobody entered / leaf / leaf on which every ray on the node ended while the
+            // walk still had rays left (the only step that needs a cross-lane minimum)
+            const bool step_classes = getenv("STEP_CLASSES") != nullptr;
+            double sc_desc = 0, sc_int = 0, sc_leaf = 0, sc_end = 0; long sc_walks = 0;
             long nwave = 0;
             std::mt19937 rg2(7);
             const int stride = getenv("WSTRIDE") ? atoi(getenv("WSTRIDE")) : 4;   // every stride-th tile in x and y
@@ -1000,6 +1006,7 @@ int main(int argc, char** argv) {
                     const int R = 64 * K;
                     std::vector<std::vector<uint32_t>> seq(R);
                     std::vector<std::vector<int>> bvis(R);      // binary skip-pointer walk: visited nodes
+                    std::vector<char> bocc(R, 0);               // ... and whether it ended at an occluder
                     std::vector<uint64_t> key[4];
                     for (int g = 0; g < 4; ++g) key[g].resize(R);
                     for (int c = 0; c < K; ++c)
@@ -1022,7 +1029,29 @@ int main(int argc, char** argv) {
                             float dist = std::sqrt(dot(sd, sd));
                             sd = sd * (1.0f / std::max(dist, 1e-20f));
                             emu_walk(WN, pr, Ray{org[l], sd, 0.01f, dist - 0.001f, true}, true, 8, &seq[r]);
-                            walk(Fr, Ray{org[l], sd, 0.01f, dist - 0.001f, true}, true, &bvis[r]);
+                            bocc[r] = walk(Fr, Ray{org[l], sd, 0.01f, dist - 0.001f, true}, true, &bvis[r]).occ;
+                        }
+                    if (step_classes)
+                        for (int c = 0; c + 1 < K; c += 2) {
+                            struct On { int node; bool desc, ended; };
+                            std::vector<On> on;
+                            for (int r = c * 64; r < (c + 2) * 64; ++r)
+                                for (size_t i = 0; i < bvis[r].size(); ++i) {
+                                    const int m = bvis[r][i];
+                                    on.push_back({m, Fr.n[m].cnt == 0 && i + 1 < bvis[r].size() && bvis[r][i + 1] == m + 1,
+                                                  bocc[r] && i + 1 == bvis[r].size()});
+                                }
+                            if (on.empty()) continue;
+                            std::sort(on.begin(), on.end(), [](const On& a, const On& b) { return a.node < b.node; });
+                            ++sc_walks;
+                            for (size_t i = 0; i < on.size();) {
+                                size_t j = i; bool desc = false, all_ended = true;
+                                for (; j < on.size() && on[j].node == on[i].node; ++j) { desc |= on[j].desc; all_ended &= on[j].ended; }
+                                if (Fr.n[on[i].node].cnt > 0) { sc_leaf += 1; sc_end += all_ended && j < on.size(); }
+                                else if (desc) sc_desc += 1;
+                                else sc_int += 1;
+                                i = j;
+                            }
                         }
                     for (int g = 0; g < 4; ++g) {
                         std::sort(key[g].begin(), key[g].end());
@@ -1056,6 +1085,10 @@ int main(int argc, char** argv) {
                 printf("  %-26s steps per wave %.1f, distinct node fetches per wave %.1f (per step %.2f) | binary lockstep union %.1f"
                        " | wide lockstep union %.1f\n",
                        names[g], st[g] / nwave, ds[g] / nwave, ds[g] / st[g], bu[g] / nwave, wu[g] / nwave);
+            if (step_classes && sc_walks)
+                printf("step classes per pair walk (%ld walks): %.1f steps = %.1f descend + %.1f interior no-descend + %.1f leaf;"
+                       " all-ended leaf steps with rays remaining %.2f\n", sc_walks, (sc_desc + sc_int + sc_leaf) / sc_walks,
+                       sc_desc / sc_walks, sc_int / sc_walks, sc_leaf / sc_walks, sc_end / sc_walks);
         }
         double wsum = 0; for (int v : wave_it) wsum += v;
         printf("emu: primary iters %.2f tris %.2f | bounce iters %.2f tris %.2f | shadow iters %.2f tris %.2f lost %.4f max stack %d wave-max iters %.1f | mismatches %ld | nodes %zu\n",
