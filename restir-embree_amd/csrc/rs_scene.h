@@ -548,6 +548,26 @@ __device__ __forceinline__ bool box_test_walk(float4 a, float4 b, vec3 o, vec3 i
 #endif
 }
 
+// A wave-uniform value copied into a VGPR once (the compiler otherwise re-materialises it inside every exec-masked
+// region that selects with it).
+__device__ __forceinline__ uint32_t walk_vgpr(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
+// One ray's part of an interior step at node m: inside its own cur == m region the ray tests the box and moves its
+// cursor to `down` (= m + 1, entered) or to `skip` (= skip(m)).  Returns whether it entered (false off the node).
+__device__ __forceinline__ bool lockstep_enter(uint32_t& cur, uint32_t m, uint32_t down, uint32_t skip, float4 a, float4 b,
+                                               vec3 o, vec3 inv, float tnear_c, float tfar_c) {
+    bool h = false;
+    if (cur == m) {
+        h = box_test_walk(a, b, o, inv, tnear_c, tfar_c);
+        cur = h ? down : skip;
+    }
+    return h;
+}
+
 // K any-hit rays per lane sharing one origin (a pixel's shadow rays to K light samples), one lockstep
 // walk: each lane keeps K cursors, the wave steps through the union of all 64*K paths; each step's node
 // (and leaf triangles) is loaded once and tested against every ray whose cursor is on it.
@@ -572,6 +592,9 @@ __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const boo
     // bools carried across the loop's control flow would live as SGPR lane masks re-merged with
     // s_andn2/s_and/s_or at every join -- that bookkeeping made SALU the busiest unit.  Only
     // wave-uniform branches remain (leaf or not, ballot tests).
+    // The leaf branch comes first: it is known as soon as the node is in SGPRs.  An interior step keeps nothing
+    // but the cursors -- each ray moves its own inside its cur[k] == m region, straight from its box test -- and
+    // "some ray descended" is the OR of the rays' test masks.
     uint32_t occb = 0u;
     uint32_t m = lockstep_first(__ballot(live) != 0);
     while (m < n) {
@@ -579,11 +602,11 @@ __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const boo
         node_load(S.nodes, m, a, b);
         const uint32_t skip = (uint32_t)__float_as_int(a.w);
         const int leaf = __float_as_int(b.w);
-        uint32_t hbb = 0u;
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-            hbb |= (cur[k] == m && box_test_walk(a, b, o, inv[k], tnear_c, tfar_c[k])) ? (1u << k) : 0u;
         if (leaf >= 0) {                                      // wave-uniform
+            uint32_t hbb = 0u;
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                hbb |= (cur[k] == m && box_test_walk(a, b, o, inv[k], tnear_c, tfar_c[k])) ? (1u << k) : 0u;
             const int first = leaf >> 3, cnt = (leaf & 7) + 1;
             for (int j = 0; j < cnt; ++j) {
                 const uint32_t want = hbb & ~occb;
@@ -608,9 +631,12 @@ __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const boo
             }
             m = lockstep_step(true, false, survivor, m, skip, lane_min<K>(cur));
         } else {
+            const uint32_t down_v = walk_vgpr(m + 1u), skip_v = walk_vgpr(skip);
+            bool desc = false;
 #pragma unroll
-            for (int k = 0; k < K; ++k) cur[k] = cur[k] == m ? ((hbb >> k) & 1u ? m + 1 : skip) : cur[k];
-            m = lockstep_step(false, hbb != 0u, false, m, skip, 0u);
+            for (int k = 0; k < K; ++k)
+                desc |= lockstep_enter(cur[k], m, down_v, skip_v, a, b, o, inv[k], tnear_c, tfar_c[k]);
+            m = lockstep_step(false, desc, false, m, skip, 0u);
         }
     }
 #pragma unroll
@@ -629,9 +655,9 @@ __device__ __forceinline__ bool occluded_wave(const DevScene& S, bool active, ve
         node_load(S.nodes, m, a, b);
         const uint32_t skip = (uint32_t)__float_as_int(a.w);
         const int leaf = __float_as_int(b.w);
-        const bool at = i == m;
-        const bool hb = at && box_test_walk(a, b, o, inv, tnear_c, tfar_c);
         if (leaf >= 0) {                                      // wave-uniform
+            const bool at = i == m;
+            const bool hb = at && box_test_walk(a, b, o, inv, tnear_c, tfar_c);
             const int first = leaf >> 3, cnt = (leaf & 7) + 1;
             for (int k = 0; k < cnt; ++k) {
                 const bool want = hb && occ == 0u;
@@ -646,8 +672,8 @@ __device__ __forceinline__ bool occluded_wave(const DevScene& S, bool active, ve
             i = at ? (ended ? kLockstepDone : skip) : i;
             m = lockstep_step(true, false, at && !ended, m, skip, i);
         } else {
-            i = at ? (hb ? m + 1 : skip) : i;
-            m = lockstep_step(false, hb, false, m, skip, 0u);
+            const bool desc = lockstep_enter(i, m, m + 1u, skip, a, b, o, inv, tnear_c, tfar_c);
+            m = lockstep_step(false, desc, false, m, skip, 0u);
         }
     }
     return occ != 0u;
@@ -665,9 +691,9 @@ __device__ __forceinline__ Hit closest_wave(const DevScene& S, bool active, vec3
         node_load(S.nodes, m, a, b);
         const uint32_t skip = (uint32_t)__float_as_int(a.w);
         const int leaf = __float_as_int(b.w);
-        const bool at = i == m;
-        const bool hb = at && box_test_m(a, b, mo.lo, mo.hi, inv, tnear, h.t);
         if (leaf >= 0) {                                      // wave-uniform
+            const bool at = i == m;
+            const bool hb = at && box_test_m(a, b, mo.lo, mo.hi, inv, tnear, h.t);
             if (__ballot(hb) != 0) {
                 const int first = leaf >> 3, cnt = (leaf & 7) + 1;
                 for (int k = 0; k < cnt; ++k) {
@@ -685,7 +711,11 @@ __device__ __forceinline__ Hit closest_wave(const DevScene& S, bool active, vec3
             i = at ? skip : i;
             m = lockstep_next(true, false, true, m, skip);    // the ray(s) on m go on
         } else {
-            i = at ? (hb ? m + 1 : skip) : i;
+            bool hb = false;
+            if (i == m) {                                     // the ray's own region, as lockstep_enter
+                hb = box_test_m(a, b, mo.lo, mo.hi, inv, tnear, h.t);
+                i = hb ? m + 1u : skip;
+            }
             m = lockstep_next(false, __ballot(hb) != 0, false, m, skip);
         }
     }

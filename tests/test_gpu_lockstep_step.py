@@ -1,0 +1,110 @@
+"""The lockstep walks' step (rs_scene.h occluded_wave_multi / occluded_wave / closest_wave) branches on the leaf flag
+first, and on an interior node each ray tests the box and moves its cursor inside its own region (lockstep_enter).
+No value may change: frames, reservoirs and the ray counter of the lockstep kernels against the per-lane walks, and
+frames and reservoirs against the oracle, all with np.array_equal.
+
+(m_area, m_brdf): with two area candidates per walk the last batch is full (2, 32), half full (1, 3) or absent (0);
+the BRDF candidate (a one-ray walk of its own) is absent, single or double.
+Scenes: C2's generator with 64 lights, the same under a quad that hides the ceiling lights (every ceiling-bound shadow
+ray ends in its first leaf), and with 0.2 m lights, where the BRDF candidate's ray exists in most lanes (a cosine
+direction rarely lands on a 0.02 m quad).  The walk kind is pinned and the candidate-split pass switched off, and both
+are asserted after the frames, as tests/test_gpu_light_lds.py does.
+"""
+import numpy as np
+import pytest
+
+import oracle_lib as O
+from restir_amd import params as P
+from restir_amd import scenes
+from restir_amd.renderer import Renderer
+
+pytestmark = pytest.mark.gpu
+
+N_FRAMES = 2
+PAIRS = [(1, 1), (2, 1), (3, 1), (32, 1), (2, 0), (0, 1), (2, 2)]
+SHAPES = [("c2", 64, 64), ("c2", 50, 38), ("blocker", 50, 38), ("big_lights", 50, 38)]
+
+
+def _blocker(sc):
+    """sc with a quad 5 mm under the ceiling lights (z = 1.985), facing down, one more white material."""
+    z = 1.98
+    p = np.array([[-0.97, -0.97, z, -0.97, 0.97, z, 0.97, 0.97, z],
+                  [-0.97, -0.97, z, 0.97, 0.97, z, 0.97, -0.97, z]], np.float32)
+    n = np.tile(np.array([0, 0, -1], np.float32), (2, 3))
+    mats = list(sc.materials) + [scenes.Material(kd=(0.73, 0.73, 0.73), type=scenes.LAMBERT, shininess=1.0)]
+    return scenes.Scene(positions=np.concatenate([sc.positions, p]), normals=np.concatenate([sc.normals, n]),
+                        tri_material=np.concatenate([sc.tri_material, np.full(2, len(mats) - 1, np.uint32)]),
+                        materials=mats, camera=sc.camera, name="c2_64_blocker")
+
+
+@pytest.fixture(scope="module")
+def world():
+    """name -> (scene, its oracle scene), built once"""
+    sc = {"c2": scenes.cornell_many_lights(64), "big_lights": scenes.cornell_many_lights(64, size=0.2)}
+    sc["blocker"] = _blocker(sc["c2"])
+    return {k: (v, O.OracleScene(v)) for k, v in sc.items()}
+
+
+def _cam(sc, f):
+    return scenes.orbit_camera(sc.camera, f, 48, 0.2)
+
+
+def _gpu(sc, W, H, prm, walk):
+    """(frames, reservoirs after the last frame, rays of all frames) with the walks pinned to `walk`"""
+    g = Renderer(W, H)
+    g.set_traversal(walk)
+    g.set_initial_split("off")
+    gs = g.load_scene(sc)
+    frames, rays = [], 0
+    for f in range(N_FRAMES):
+        frames.append(g.produce_restir(gs, _cam(sc, f), prm, f).copy())
+        rays += int(g.last_times.rays)
+    assert g.initial_split()[1] is False, "the last frame's initial pass ran candidate-split"
+    assert g.traversal()[1] == (0 if walk == "lockstep" else 1), "the last frame did not walk as pinned"
+    res = g.reservoirs()
+    gs.close()
+    g.close()
+    return frames, res, rays
+
+
+def _oracle(sc, osc, W, H, prm):
+    o = O.OracleRenderer(W, H)
+    return [o.render(osc, _cam(sc, f), prm, f) for f in range(N_FRAMES)], o.reservoirs()
+
+
+def _same(a, b, what):
+    assert np.isfinite(a).all(), what
+    assert np.array_equal(a, b), f"{what}: {int(np.any(a != b, -1).sum())} px differ"
+
+
+def _check(world, which, W, H, prm, what):
+    sc, osc = world[which]
+    fa, ra, na = _gpu(sc, W, H, prm, "lockstep")
+    fb, rb, nb = _gpu(sc, W, H, prm, "lane")
+    fo, ro = _oracle(sc, osc, W, H, prm)
+    for f in range(N_FRAMES):
+        _same(fa[f], fb[f], f"{what} frame {f}, lockstep vs per-lane")
+        _same(fa[f], fo[f], f"{what} frame {f}, lockstep vs oracle")
+    _same(ra, rb, f"{what} reservoirs, lockstep vs per-lane")
+    _same(ra, ro, f"{what} reservoirs, lockstep vs oracle")
+    assert na == nb and na > 0, f"{what}: {na} rays in lockstep, {nb} per lane"
+
+
+@pytest.mark.parametrize("m_area,m_brdf", PAIRS)
+@pytest.mark.parametrize("which,W,H", SHAPES)
+def test_initial_pass(world, which, W, H, m_area, m_brdf):
+    _check(world, which, W, H, P.default_params(m_area=m_area, m_brdf=m_brdf), f"{which} {W}x{H} ({m_area}, {m_brdf})")
+
+
+@pytest.mark.parametrize("which", ["c2", "big_lights"])
+def test_visibility_pass(world, which):
+    """do_visibility_pass: the initial pass traces no shadow ray, the visibility pass walks one ray per lane"""
+    _check(world, which, 50, 38, P.default_params(m_area=2, m_brdf=1, do_visibility_pass=1), f"{which} visibility pass")
+
+
+@pytest.mark.parametrize("which", ["blocker", "big_lights"])
+def test_spatial_reuse(world, which):
+    """k = 4 neighbours: k_spatial pairs its shadow rays through the same walk"""
+    prm = P.metric_params(m_area=3, m_brdf=1)
+    assert prm.do_spatial == 1 and prm.spatial_neighbors == 4
+    _check(world, which, 50, 38, prm, f"{which} spatial")
