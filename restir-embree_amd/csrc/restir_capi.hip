@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <type_traits>
 
 namespace rs {
 int build_bvh(const float* d_pos, uint32_t n, hipStream_t st, float4** d_nodes, uint32_t* n_nodes, float4** d_tris,
@@ -1334,33 +1335,23 @@ extern "C" int rs_scene_info(const rs_scene* s, uint32_t* n_tris, uint32_t* n_em
 // --------------------------------------------------------------------------- frame / tile driver
 static dim3 grid_rows(int W, int ya, int yb) { return dim3((W + 15) / 16, (yb - ya + 15) / 16); }
 
-// launch kernel<Trav> for the frame's traversal kind
-// the kernel instantiation of the frame: walk kind | TRAV_WIDE when the scene's 8-wide tree is live
-// (rs_scene.h Trav; c->twide is taken from the scene when the frame begins)
-#define LAUNCH_TRAV_BS_SH_ON(c, st, kernel, grid, bs, sh, ...)                                              \
-    do {                                                                                                   \
-        switch ((c)->trav | ((c)->twide ? TRAV_WIDE : 0)) {                                                \
-            case TRAV_LANE | TRAV_WIDE: kernel<TRAV_LANE | TRAV_WIDE><<<(grid), (bs), (sh), (st)>>>(__VA_ARGS__); break; \
-            case TRAV_LANE: kernel<TRAV_LANE><<<(grid), (bs), (sh), (st)>>>(__VA_ARGS__); break;                  \
-            case TRAV_WIDE: kernel<TRAV_LOCKSTEP | TRAV_WIDE><<<(grid), (bs), (sh), (st)>>>(__VA_ARGS__); break;  \
-            default: kernel<TRAV_LOCKSTEP><<<(grid), (bs), (sh), (st)>>>(__VA_ARGS__); break;                     \
-        }                                                                                                  \
-    } while (0)
-#define LAUNCH_TRAV_BS_ON(c, st, kernel, grid, bs, ...) LAUNCH_TRAV_BS_SH_ON(c, st, kernel, grid, bs, 0, __VA_ARGS__)
-#define LAUNCH_TRAV_BS_SH(c, kernel, grid, bs, sh, ...) LAUNCH_TRAV_BS_SH_ON(c, (c)->fs, kernel, grid, bs, sh, __VA_ARGS__)
-// the same with extra template bits X (a pass's own variant bits above the traversal kind's)
-#define LAUNCH_TRAV_X(c, X, kernel, grid, ...)                                                              \
-    do {                                                                                                   \
-        switch ((c)->trav | ((c)->twide ? TRAV_WIDE : 0)) {                                                \
-            case TRAV_LANE | TRAV_WIDE: kernel<TRAV_LANE | TRAV_WIDE | (X)><<<(grid), 256, 0, (c)->fs>>>(__VA_ARGS__); break; \
-            case TRAV_LANE: kernel<TRAV_LANE | (X)><<<(grid), 256, 0, (c)->fs>>>(__VA_ARGS__); break;                  \
-            case TRAV_WIDE: kernel<TRAV_LOCKSTEP | TRAV_WIDE | (X)><<<(grid), 256, 0, (c)->fs>>>(__VA_ARGS__); break;  \
-            default: kernel<TRAV_LOCKSTEP | (X)><<<(grid), 256, 0, (c)->fs>>>(__VA_ARGS__); break;                     \
-        }                                                                                                  \
-    } while (0)
-#define LAUNCH_TRAV_ON(c, st, kernel, grid, ...) LAUNCH_TRAV_BS_ON(c, st, kernel, grid, 256, __VA_ARGS__)
-#define LAUNCH_TRAV(c, kernel, grid, ...) LAUNCH_TRAV_ON(c, (c)->fs, kernel, grid, __VA_ARGS__)
-#define LAUNCH_TRAV_BS(c, kernel, grid, bs, ...) LAUNCH_TRAV_BS_ON(c, (c)->fs, kernel, grid, bs, __VA_ARGS__)
+// The kernel instantiation of the frame: walk kind | TRAV_WIDE when the scene's 8-wide tree is live (rs_scene.h Trav;
+// c->twide is taken from the scene when the frame begins).  The one switch over the kind: f gets it as a compile-time
+// constant T (T() in a template argument) and names the kernel, its own variant bits, grid, block, LDS and stream.
+template <int T> using Kind = std::integral_constant<int, T>;
+template <class Fn>
+static auto with_trav(const rs_context* c, Fn&& f) {
+    switch (c->trav | (c->twide ? TRAV_WIDE : 0)) {
+        case TRAV_LANE | TRAV_WIDE: return f(Kind<TRAV_LANE | TRAV_WIDE>{});
+        case TRAV_LANE: return f(Kind<TRAV_LANE>{});
+        case TRAV_WIDE: return f(Kind<TRAV_LOCKSTEP | TRAV_WIDE>{});
+        default: return f(Kind<TRAV_LOCKSTEP>{});
+    }
+}
+// a run-time flag as a compile-time constant (a pass's own variant bits).  Kernels are laid out in the code object in
+// the order the nesting instantiates them: 1 before 0, the outer choice slowest.
+template <class Fn>
+static auto with_flag(bool b, Fn&& f) { return b ? f(Kind<1>{}) : f(Kind<0>{}); }
 
 // fold a finished frame's pass times (event-ring slot s) into the running totals
 static void fold_slot(rs_context* c, int s) {
@@ -1518,16 +1509,11 @@ static bool want_split(const rs_context* c, const rs_frame_params* P, int gy0, i
 // the one-launch kernel.
 constexpr int kPersistSortedWgs = 3;
 static int persist_sorted_wgs(rs_context* c) {
-    const int kind = c->trav | (c->twide ? TRAV_WIDE : 0);
-    int& n = c->persist_sorted_wgs[kind];
+    int& n = c->persist_sorted_wgs[c->trav | (c->twide ? TRAV_WIDE : 0)];
     if (!n) {
-        hipError_t e = hipSuccess;
-        switch (kind) {
-            case TRAV_LANE | TRAV_WIDE: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_gbuffer_initial_sorted_pq<TRAV_LANE | TRAV_WIDE>, 256, 0); break;
-            case TRAV_LANE: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_gbuffer_initial_sorted_pq<TRAV_LANE>, 256, 0); break;
-            case TRAV_WIDE: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_gbuffer_initial_sorted_pq<TRAV_WIDE>, 256, 0); break;
-            default: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_gbuffer_initial_sorted_pq<TRAV_LOCKSTEP>, 256, 0); break;
-        }
+        const hipError_t e = with_trav(c, [&](auto T) {
+            return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_gbuffer_initial_sorted_pq<T()>, 256, 0);
+        });
         if (e != hipSuccess || n <= 0) n = RS_INITIAL_WAVES_SORT;
     }
     return n;
@@ -1714,15 +1700,18 @@ extern "C" int rs_tile_begin(rs_context* c, const rs_scene* s, const rs_camera* 
             FrameConst Fm = F;
             Fm.gy0 = r[0]; Fm.gy1 = r[1];
             const dim3 gm = grid_rows(c->W, r[0], r[1]);
-            LAUNCH_TRAV(c, k_gbuffer_initial, gm, S, Fm, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, 0, count_slot(c, gm));
+            with_trav(c, [&](auto T) {
+                k_gbuffer_initial<T()><<<gm, 256, 0, c->fs>>>(S, Fm, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, 0, count_slot(c, gm));
+            });
             HIPCHK(c, hipGetLastError());
         }
     }
     if (c->split) {
         const dim3 gs = grid_split(c->W, Fi.gy0, Fi.gy1);
-        LAUNCH_TRAV_BS_SH(c, k_gbuffer_initial_split, gs, 64 * kSplit, split_lds_bytes(P->m_area + P->m_brdf, P->m_brdf),
-                          S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb,
-                    c->shade_fused ? 1 : 0, count_slot(c, gs, kSplit));
+        with_trav(c, [&](auto T) {
+            k_gbuffer_initial_split<T()><<<gs, 64 * kSplit, split_lds_bytes(P->m_area + P->m_brdf, P->m_brdf), c->fs>>>(
+                S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, c->shade_fused ? 1 : 0, count_slot(c, gs, kSplit));
+        });
     } else if (init_kind > 0) {
         Fi.cand_w = c->candw[c->li];
         Fi.cand_ray = c->candr[c->li];
@@ -1732,28 +1721,37 @@ extern "C" int rs_tile_begin(rs_context* c, const rs_scene* s, const rs_camera* 
             // leave every later one pulling past the end)
             const uint32_t nt = gg.x * gg.y * 4u;
             HIPCHK(c, hipMemsetAsync(c->qctr[c->li], 0, 4 * sizeof(uint32_t), c->fs));
-            LAUNCH_TRAV(c, k_gbuffer_initial_sorted_pq, gp, S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb,
-                        c->shade_fused ? 1 : 0, count_slot(c, gp), TileQ{c->qctr[c->li], nt});
+            with_trav(c, [&](auto T) {
+                k_gbuffer_initial_sorted_pq<T()><<<gp, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb,
+                                                                         c->shade_fused ? 1 : 0, count_slot(c, gp),
+                                                                         TileQ{c->qctr[c->li], nt});
+            });
         } else {
-            LAUNCH_TRAV(c, k_gbuffer_initial_sorted, gg, S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, c->shade_fused ? 1 : 0,
-                        count_slot(c, gg));
+            with_trav(c, [&](auto T) {
+                k_gbuffer_initial_sorted<T()><<<gg, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb,
+                                                                      c->shade_fused ? 1 : 0, count_slot(c, gg));
+            });
         }
-    } else if (use_light_lds(c, P, s)) {
-        const CountSlot cs = count_slot(c, gg);
-        if (c->twide)
-            k_gbuffer_initial<TRAV_LOCKSTEP | TRAV_WIDE | LIGHT_LDS><<<gg, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb,
-                                                                                 c->shade_fused ? 1 : 0, cs);
-        else
-            k_gbuffer_initial<TRAV_LOCKSTEP | LIGHT_LDS><<<gg, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb,
-                                                                     c->shade_fused ? 1 : 0, cs);
     } else {
-        LAUNCH_TRAV(c, k_gbuffer_initial, gg, S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, c->shade_fused ? 1 : 0,
-                    count_slot(c, gg));
+        const bool lds = use_light_lds(c, P, s);          // lockstep kinds only: LIGHT_LDS exists for those two
+        with_trav(c, [&](auto T) {
+            const CountSlot cs = count_slot(c, gg);
+            const int fuse = c->shade_fused ? 1 : 0;
+            if constexpr (!trav_lane(T())) {
+                if (lds) {
+                    k_gbuffer_initial<T() | LIGHT_LDS><<<gg, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, fuse, cs);
+                    return;
+                }
+            }
+            k_gbuffer_initial<T()><<<gg, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, fuse, cs);
+        });
     }
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev[EV_INIT], c->fs));
     if (P->do_visibility_pass) {
-        LAUNCH_TRAV(c, k_visibility, gb, S, F, c->G[gnew], ResBuf{c->R[c->ra]}, count_slot(c, gb));
+        with_trav(c, [&](auto T) {
+            k_visibility<T()><<<gb, 256, 0, c->fs>>>(S, F, c->G[gnew], ResBuf{c->R[c->ra]}, count_slot(c, gb));
+        });
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(c->ev[EV_VIS], c->fs));
@@ -1814,13 +1812,11 @@ extern "C" int rs_tile_temporal(rs_context* c) {
         // the wave-sorted shadow rays (TEMPORAL_SORT) unless RESTIR_SORT_TEMPORAL=off: C3 (per-lane) temporal
         // 1.54 -> 1.36 ms, C5 (lockstep) 0.210 -> 0.191 ms
         const bool tsort = c->sort_temporal != RS_SPLIT_OFF;
-#define RS_TEMPORAL_ARGS S, Sp, c->F, c->G[c->gcur], c->G[c->gprev], ResBuf{c->R[c->rcur]}, ResBuf{c->R[c->last]}, \
-                         ResBuf{c->R[c->rb]}, count_slot(c, gb)
-        if (partial && tsort) LAUNCH_TRAV_X(c, TEMPORAL_BAND | TEMPORAL_SORT, k_temporal, gb, RS_TEMPORAL_ARGS);
-        else if (partial) LAUNCH_TRAV_X(c, TEMPORAL_BAND, k_temporal, gb, RS_TEMPORAL_ARGS);
-        else if (tsort) LAUNCH_TRAV_X(c, TEMPORAL_SORT, k_temporal, gb, RS_TEMPORAL_ARGS);
-        else LAUNCH_TRAV(c, k_temporal, gb, RS_TEMPORAL_ARGS);
-#undef RS_TEMPORAL_ARGS
+        with_flag(partial, [&](auto Band) { with_flag(tsort, [&](auto Sort) { with_trav(c, [&](auto T) {
+            k_temporal<T() | (Band() ? TEMPORAL_BAND : 0) | (Sort() ? TEMPORAL_SORT : 0)><<<gb, 256, 0, c->fs>>>(
+                S, Sp, c->F, c->G[c->gcur], c->G[c->gprev], ResBuf{c->R[c->rcur]}, ResBuf{c->R[c->last]}, ResBuf{c->R[c->rb]},
+                count_slot(c, gb));
+        }); }); });
         c->twide = twide;
         HIPCHK(c, hipGetLastError());
         if (c->F.debug_reproj) {
@@ -1866,21 +1862,19 @@ extern "C" int rs_tile_spatial(rs_context* c, int pass_index) {
         const bool cm = c->F.mis == MIS_CONSTANT;
         const bool tev = c->tuning && c->tune_n + 2 <= (int)(sizeof(c->tune_ev) / sizeof(c->tune_ev[0]));
         if (tev) HIPCHK(c, hipEventRecord(c->tune_ev[c->tune_n], c->fs));
-#define SPATIAL(TK, CM, SM) k_spatial<TK, CM, SM><<<gb, 256, 0, c->fs>>>(S, c->F, G, Rr, Rw, pass_index, fuse, c->fb, cs)
         const bool ssort = c->sort_spatial == RS_SPLIT_ON || (c->sort_spatial == RS_SPLIT_AUTO && c->trav == TRAV_LANE);
         if (ssort && cm && c->F.k + 1 <= kSpatialSortMax) {
-            LAUNCH_TRAV(c, k_spatial_sorted, gb, S, c->F, G, Rr, Rw, pass_index, fuse, c->fb, cs);
-        } else if (c->trav == TRAV_LANE) {
-            if (c->twide) { if (cm) SPATIAL(TRAV_LANE | TRAV_WIDE, 1, 0); else SPATIAL(TRAV_LANE | TRAV_WIDE, 0, 0); }
-            else { if (cm) SPATIAL(TRAV_LANE, 1, 0); else SPATIAL(TRAV_LANE, 0, 0); }
-        } else if (grid_waves(gb) < (size_t)2 * c->wave_slots) {   // a small launch: RS_SPATIAL_WAVES_SMALL budget
-            if (c->twide) { if (cm) SPATIAL(TRAV_WIDE, 1, 1); else SPATIAL(TRAV_WIDE, 0, 1); }
-            else { if (cm) SPATIAL(TRAV_LOCKSTEP, 1, 1); else SPATIAL(TRAV_LOCKSTEP, 0, 1); }
+            with_trav(c, [&](auto T) {
+                k_spatial_sorted<T()><<<gb, 256, 0, c->fs>>>(S, c->F, G, Rr, Rw, pass_index, fuse, c->fb, cs);
+            });
         } else {
-            if (c->twide) { if (cm) SPATIAL(TRAV_WIDE, 1, 0); else SPATIAL(TRAV_WIDE, 0, 0); }
-            else { if (cm) SPATIAL(TRAV_LOCKSTEP, 1, 0); else SPATIAL(TRAV_LOCKSTEP, 0, 0); }
+            // a small lockstep launch takes the RS_SPATIAL_WAVES_SMALL budget (the per-lane kinds have one budget)
+            const bool small = grid_waves(gb) < (size_t)2 * c->wave_slots;
+            with_flag(small, [&](auto Small) { with_trav(c, [&](auto T) { with_flag(cm, [&](auto CM) {
+                constexpr int SM = trav_lane(T()) ? 0 : Small();
+                k_spatial<T(), CM(), SM><<<gb, 256, 0, c->fs>>>(S, c->F, G, Rr, Rw, pass_index, fuse, c->fb, cs);
+            }); }); });
         }
-#undef SPATIAL
         if (tev) {
             HIPCHK(c, hipEventRecord(c->tune_ev[c->tune_n + 1], c->fs));
             c->tune_n += 2;
@@ -1909,7 +1903,9 @@ extern "C" int rs_tile_finish(rs_context* c, const float** band_rgb, rs_pass_tim
     if (!c->shade_fused) {
         const DevScene S = c->scene->dev();
         const dim3 gb = grid_rows(c->W, c->F.y0, c->F.y1);
-        LAUNCH_TRAV(c, k_shade, gb, S, c->F, c->G[c->gcur], ResBuf{c->R[c->rcur]}, c->fb, count_slot(c, gb));
+        with_trav(c, [&](auto T) {
+            k_shade<T()><<<gb, 256, 0, c->fs>>>(S, c->F, c->G[c->gcur], ResBuf{c->R[c->rcur]}, c->fb, count_slot(c, gb));
+        });
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(c->ev[EV_SHADE], c->fs));
@@ -2022,7 +2018,7 @@ extern "C" int rs_render_direct_mis(rs_context* c, const rs_scene* s, const rs_c
     pick_traversal(c, s);
     c->twide = s->wide_on;
     c->tuning = false;               // the ReSTIR frames own the per-scene traversal tuning
-    LAUNCH_TRAV(c, k_direct_mis, g, S, F, (int)spp, c->fb, count_slot(c, g));
+    with_trav(c, [&](auto T) { k_direct_mis<T()><<<g, 256, 0, c->fs>>>(S, F, (int)spp, c->fb, count_slot(c, g)); });
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(e1, c->stream));
     k_reduce_counts<<<kReduceBlocks, kReduceThreads, 0, c->stream>>>(c->d_part, c->part_used, c->d_red,

@@ -22,7 +22,7 @@
 
 // waves per SIMD the ray-tracing kernels are register-budgeted for (launch_bounds 2nd argument)
 #ifndef RS_INITIAL_WAVES
-#define RS_INITIAL_WAVES 4
+#define RS_INITIAL_WAVES 5
 #endif
 #ifndef RS_SPATIAL_WAVES
 #define RS_SPATIAL_WAVES 4
@@ -31,20 +31,20 @@
 // other frames in flight (C2 balanced bands, 5 vs 4 waves: 1/4 band 0.373 vs 0.383 ms/frame, 1/8 band
 // 0.241 vs 0.244; a full-size launch stays at 4: 5 cost C5 3.7 %)
 #ifndef RS_SPATIAL_WAVES_SMALL
-#define RS_SPATIAL_WAVES_SMALL RS_SPATIAL_WAVES
+#define RS_SPATIAL_WAVES_SMALL 5
 #endif
-// ... for the per-lane traversal kind (incoherent scenes: the walk loop needs more registers)
+// ... for the per-lane traversal kind (incoherent scenes), budgeted apart: one wave more than the lockstep kind
 #ifndef RS_INITIAL_WAVES_LANE
-#define RS_INITIAL_WAVES_LANE RS_INITIAL_WAVES
+#define RS_INITIAL_WAVES_LANE 6
 #endif
 #ifndef RS_SPATIAL_WAVES_LANE
-#define RS_SPATIAL_WAVES_LANE RS_SPATIAL_WAVES
+#define RS_SPATIAL_WAVES_LANE 5
 #endif
 #ifndef RS_TEMPORAL_WAVES
 #define RS_TEMPORAL_WAVES 4
 #endif
 #ifndef RS_TEMPORAL_WAVES_LANE
-#define RS_TEMPORAL_WAVES_LANE RS_TEMPORAL_WAVES
+#define RS_TEMPORAL_WAVES_LANE 5
 #endif
 #define RS_WAVES(T, lockstep, lane) (((T) & TRAV_LANE) ? (lane) : (lockstep))
 // area candidates whose shadow rays share one lockstep traversal (occluded_wave_multi); 4 measured on
@@ -80,8 +80,8 @@ struct FrameConst {
     int canon_vis;        // spatial pass: the canonical (own) reservoir's sample is known unoccluded from the pixel
                           //   (restir_capi.hip rs_tile_spatial; §3.2) -- its visibility ray is not traced again
     uint8_t* dbg;         // 2 x W*H bytes: [p] the pixel's own rejection (1..3), [W*H + p] forward-check hit
-    float* cand_w;        // the sorted initial pass's phase-A candidate weights (RS_SORT_STORE_W), per 8x8 tile
-    float4* cand_ray;     // ... and its needed shadow rays' (direction, tfar) (RS_SORT_STORE_RAY), per 8x8 tile
+    float* cand_w;        // the sorted initial pass's phase-A candidate weights (sorted_tile), per hand-off slot
+    float4* cand_ray;     // ... and its needed shadow rays' (direction, tfar), per hand-off slot
 };
 
 struct Counters { unsigned long long rays, primary, reproj_outside; };   // per-frame totals
@@ -106,12 +106,9 @@ __device__ __forceinline__ uint64_t wave_clock() { return __builtin_amdgcn_s_mem
 // load-balancing record (rs_mgpu_rebalance, TiledRenderer.rebalance): the wave's lifetime spread evenly over the 8
 // rows of its 8x8 tile from its top row (lanes 0..7 one row each), so band boundaries balance to the row rather than
 // to the tile row.  Row-spread atomics, only while tracking is on (calibration frames).
-#ifndef RS_ROWCOST_SPREAD
-#define RS_ROWCOST_SPREAD 1    // 0: the whole wave's time on its top row (round 4)
-#endif
 __device__ __forceinline__ void row_cost_add(CountSlot C, uint64_t t0, int y) {
     if (!C.row_cost) return;
-    constexpr int kRows = RS_ROWCOST_SPREAD ? 8 : 1;
+    constexpr int kRows = 8;
     const int yt = __builtin_amdgcn_readfirstlane(y) + (int)(threadIdx.x & 63);
     const float w = (float)(wave_clock() - t0) * (1.0f / kRows);
     if ((threadIdx.x & 63) < kRows && yt >= C.y0 && yt < C.y1) atomicAdd(C.row_cost + yt, w);
@@ -306,11 +303,7 @@ __device__ __forceinline__ GElem gbuffer_fill_cam(const DevScene& S, const Frame
         g.type = mr.type; g.kd = mr.kd; g.ks = mr.ks; g.le = mr.le; g.shin = mr.shin;
         if (g.type == MT_PHONG || g.type == MT_DIELECTRIC) {
             vec3 V = normalize(cam.pos - g.pos);
-#ifdef RS_DIAG_NO_IM   // timing diagnostic only (scripts/initial_breakdown.py); breaks parity
-            g.inv_im = 1.0f + 0.0f * dot(V, g.nrm);
-#else
             g.inv_im = 1.0f / calc_I_M(dot(V, g.nrm), g.shin);
-#endif
         }
     } else {
         g.le = F.use_sky ? sky_texel(S, dw) : F.bg;      // useSkybox ? sky : renderParams.bgColor (:231)
@@ -684,16 +677,6 @@ __device__ __forceinline__ bool pixel_of_q(const FrameConst& F, int ya, int yb, 
     y = y < yb ? y : yb - 1;
     return in;
 }
-// the unclamped origin of 8x8 tile t (pixel_of_q's layout)
-__device__ __forceinline__ void tile_origin_q(const FrameConst& F, int ya, int yb, uint32_t t, int& tx0, int& ty0) {
-    const int gx = (F.W + 15) / 16, gy = (yb - ya + 15) / 16;
-    const int q = (int)(t >> 2), w = (int)(t & 3u);
-    const int bx = q % gx;
-    int by = q / gx;
-    if (F.row_order && ya == 0 && yb == F.H && F.n_order == gy) by = order_row(F.row_order, (uint32_t)by);
-    tx0 = bx * 16 + (w & 1) * 8;
-    ty0 = ya + by * 16 + (w >> 1) * 8;
-}
 // count_rays for a persistent wave: the slot of this wave once at the end; the per-row cost per tile
 __device__ __forceinline__ void count_store(CountSlot C, uint32_t rays, uint32_t primary) {
     const uint32_t r = wave_sum(rays), p = wave_sum(primary);
@@ -758,14 +741,13 @@ __global__ void __launch_bounds__(256, RS_WAVES(T, RS_INITIAL_WAVES, RS_INITIAL_
 //      centroids; one LDS atomic), and its light and rank are kept in the slot's LDS word;
 //   then a 64-lane scan turns the bucket counts into offsets and every slot index is scattered to its place:
 //      the chunk's rays are in LDS bucket by bucket (a counting sort);
-//   B  traces them 64 at a time in that order (lane = ray): each lane re-forms its ray from the slot -- the
-//      pixel's surface point from LDS, the candidate's RNG draws, the light record -- with the operations
-//      area_sample_at / evaluate_f_pre use, so it is bit for bit the ray the pixel would trace, walks the
-//      tree (per lane: the 8-wide tree; lockstep: the wave steps through the union of its rays' binary
-//      paths, which the grouping shrinks) and sets the pixel's occlusion bit;
-//   C  re-draws each candidate (lane = pixel) for its RIS weight and runs the reference's addSample stream
-//      over the chunk in candidate order.  (Re-drawing costs one more sampling pass; keeping the weights
-//      would take 4 B per slot of LDS and cost occupancy.)
+//   B  traces them 64 at a time in that order (lane = ray): each lane takes its ray from the slot -- the
+//      pixel's surface point from LDS, phase A's (direction, tfar) from the wave's hand-off slot -- so it is
+//      bit for bit the ray the pixel would trace, walks the tree (per lane: the 8-wide tree; lockstep: the
+//      wave steps through the union of its rays' binary paths, which the grouping shrinks) and sets the
+//      pixel's occlusion bit;
+//   C  runs the reference's addSample stream over the chunk in candidate order (lane = pixel) with phase A's
+//      weights, read back from the hand-off slot.
 // Rays aimed at neighbouring lights share their upper tree paths, so a load instruction touches fewer lines
 // (CPU lab, scripts/bvh_lab.cpp COHERENCE_WAVE, C3: distinct node fetches per wave -39 %, lockstep steps
 // -13 % for 32 candidates in 64 buckets).  The results do not depend on the order rays are traced in:
@@ -780,21 +762,16 @@ __global__ void __launch_bounds__(256, RS_WAVES(T, RS_INITIAL_WAVES, RS_INITIAL_
 #define RS_INITIAL_WAVES_SORT_LOCKSTEP 5
 #endif
 constexpr int kSortChunk = RS_SORT_CHUNK;   // area candidates per sort round
-// Phase A's unoccluded candidate weights kept for phase C in global memory (one coalesced 256-B store and load
+// Phase A's unoccluded candidate weights are kept for phase C in global memory (one coalesced 256-B store and load
 // per candidate and wave: FrameConst::cand_w) instead of phase C drawing every candidate again (its light pick, the
 // emitter record gathers, the sample, both Phong powf).  The region is the wave's hand-off slot: its resident wave
 // slot in the persistent launch (reused tile after tile, so the few MB stay in the caches), its 8x8 tile in a
 // one-launch grid (restir_capi.hip ensure_handoff sizes both by the launch)
-#ifndef RS_SORT_STORE_W
-#define RS_SORT_STORE_W 1
-#endif
-static_assert(!RS_SORT_STORE_W || kSortChunk <= 16, "ok and NaN bits of a chunk share one word");
-// ... and the needed shadow rays' (direction, tfar) for phase B (one 16-B load per ray instead of re-forming it
-// from the candidate's RNG slots and the emitter's three vertices)
-#ifndef RS_SORT_STORE_RAY
-#define RS_SORT_STORE_RAY 1
-#endif
+// ... and so are the needed shadow rays' (direction, tfar) for phase B (FrameConst::cand_ray: one 16-B load per ray
+// instead of re-forming it from the candidate's RNG slots and the emitter's three vertices)
+static_assert(kSortChunk <= 16, "ok and NaN bits of a chunk share one word");
 static_assert(kSortChunk >= 1 && kSortChunk <= 32, "one occlusion word per pixel; 11-bit ranks");
+static_assert(kSortChunk >= 14, "brdf_park needs 14 slot words per lane");
 struct SortLds {                            // one wave's region (7.3 KB at 16 candidates)
     uint32_t slot[kSortChunk * 64];         // slot k * 64 + lane: light | rank in its bucket << 21
     uint16_t e[kSortChunk * 64];            // the slots of the chunk's rays, bucket by bucket
@@ -816,34 +793,26 @@ __device__ __forceinline__ uint32_t tile_pixel(const FrameConst& F, int ya, int 
     const int x = bx * 16 + (wave & 1) * 8 + (l & 7), y = ya + by * 16 + (wave >> 1) * 8 + (l >> 3);
     return (uint32_t)y * (uint32_t)F.W + (uint32_t)x;
 }
-// the bucket of a shadow ray: RS_SORT_KEY 0 = the light's Morton bucket alone; 1 (default since round 6) = the
-// direction's octant x the top 3 bits of the light's Morton bucket (CPU lab, scripts/bvh_lab.cpp COHERENCE_WAVE, 32
-// candidates: light bucket alone -- C3 wide-walk distinct fetches -39 %, C2 binary lockstep union -6 %; octant x
-// light 3 bits -- C3 -30 %, C2 -45 %.  GPU, C3 1080p, round 4: initial pass 14.97 vs 15.14 ms; round 6 with the
-// lane refill: 75.35-75.72 vs 75.11-75.39 frames/s, initial pass 11.88-11.94 vs 11.95-11.99 ms)
-#ifndef RS_SORT_KEY
-#define RS_SORT_KEY 1
-#endif
+// the bucket of a shadow ray: the direction's octant x the top 3 bits of the light's Morton bucket, not the light's
+// bucket alone (CPU lab, scripts/bvh_lab.cpp COHERENCE_WAVE, 32 candidates: light bucket alone -- C3 wide-walk
+// distinct fetches -39 %, C2 binary lockstep union -6 %; octant x light 3 bits -- C3 -30 %, C2 -45 %.  GPU, C3 1080p,
+// round 4: initial pass 14.97 vs 15.14 ms; round 6 with the lane refill: 75.35-75.72 vs 75.11-75.39 frames/s, initial pass 11.88-11.94 vs 11.95-11.99 ms)
 __device__ __forceinline__ uint32_t ray_bucket(const DevScene& S, uint32_t pick, vec3 d) {
     const uint32_t eb = S.ebucket[pick];
-    if (RS_SORT_KEY == 0) return eb;
     const uint32_t oct = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
     return (oct << 3) | (eb >> 3);
 }
 // candidate c of a pixel: area_batch's sample and unoccluded evaluation (pick, weights, shadow ray need)
 struct AreaCand { uint32_t pick, bucket; float wu; bool ok, need, wo_nan; vec3 dir; float tfar; };
-// (the sorted pass's candidates take the pow core by call: RS_SORT_POW_CALL, C3 +2 %)
-#ifndef RS_SORT_POW_CALL
-#define RS_SORT_POW_CALL 1
-#endif
+// (the sorted pass's candidates take the pow core by call, not inlined: C3 +2 %)
 __device__ __forceinline__ AreaCand area_cand(const DevScene& S, const FrameConst& F, vec3 pos, const ShadeFrame& sf,
                                               Rng& rng, int c, bool tv, bool alive, float inv_ma) {
     AreaCand a;
     a.pick = area_pick(S, rng, c);
     float Wc, mis;
     rng.n = cand_slot(c) + 1u;
-    const Sample s = area_sample_at<RS_SORT_POW_CALL>(S, F, pos, sf, rng, a.pick, Wc, mis);
-    const FPre pr = evaluate_f_pre<RS_SORT_POW_CALL>(F, s, pos, false, sf, tv, alive);
+    const Sample s = area_sample_at<true>(S, F, pos, sf, rng, a.pick, Wc, mis);
+    const FPre pr = evaluate_f_pre<true>(F, s, pos, false, sf, tv, alive);
     a.bucket = ray_bucket(S, a.pick, pr.dir);
     const float m = F.m_brdf > 0 ? mis : inv_ma;
     a.wu = m * length(pr.L) * Wc;
@@ -858,10 +827,6 @@ __device__ __forceinline__ AreaCand area_cand(const DevScene& S, const FrameCons
 
 // the sorted kernel's reservoir state around its BRDF candidates' walks: 14 words per lane in the wave's
 // slot[] region (word c at c * 64 + lane: conflict-free)
-#ifndef RS_SORT_PARK
-#define RS_SORT_PARK 1
-#endif
-static_assert(kSortChunk >= 14 || !RS_SORT_PARK, "brdf_park needs 14 slot words per lane");
 __device__ __forceinline__ void brdf_park(uint32_t* sl, int lane, const Res& r, float bp, vec3 fs) {
     const float v[14] = {r.p.x, r.p.y, r.p.z, r.n.x, r.n.y, r.n.z, r.li.x, r.li.y, r.li.z, r.wsum, bp, fs.x, fs.y, fs.z};
 #pragma unroll
@@ -874,12 +839,12 @@ __device__ __forceinline__ void brdf_unpark(const uint32_t* sl, int lane, Res& r
     r.p = mk(v[0], v[1], v[2]); r.n = mk(v[3], v[4], v[5]); r.li = mk(v[6], v[7], v[8]); r.wsum = v[9];
     bp = v[10]; fs = mk(v[11], v[12], v[13]);
 }
-// one wave's 8x8 tile of the sorted pass: lane = pixel (x, y) (clamped; `in` whether it exists), the tile's
-// unclamped origin (tx0, ty0) for the pixel index of a ray's source lane, the wave's LDS region L, its hand-off slot
+// one wave's 8x8 tile of the sorted pass: lane = pixel (x, y) (clamped; `in` whether it exists), the wave's LDS
+// region L, its hand-off slot
 template <int T>
 __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst& F, const GBuf& G, const ResBuf& Rw,
                                             float* fb, int fuse_shade, SortLds& L, int lane, int x, int y, bool in,
-                                            int tx0, int ty0, size_t hslot, uint32_t& rays) {
+                                            size_t hslot, uint32_t& rays) {
     const size_t p = (size_t)y * F.W + x;
     {
         const GElem g = gbuffer_fill<T>(S, F, x, y, in);
@@ -908,23 +873,17 @@ __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst&
                 uint32_t needm = 0u;
                 uint32_t bkt[(kSortChunk + 3) / 4] = {};                // the needed rays' buckets, 8 bits each
                 const size_t wtile = hslot;
-#if RS_SORT_STORE_W
                 uint32_t flg = 0u;                                      // bit k: ok; bit 16 + k: its occluded weight is NaN
                 float* const wst = F.cand_w + wtile * (size_t)(kSortChunk * 64) + lane;
-#endif
                 {
                     const GElem g = G.load(p);
                     const ShadeFrame sf = make_frame(g, cam);
                     for (int k = 0; k < nk; ++k) {
                         const AreaCand a = area_cand(S, F, g.pos, sf, rng, c0 + k, tv, alive, inv_ma);
-#if RS_SORT_STORE_W
                         wst[k * 64] = a.wu;
                         flg |= (a.ok ? 1u << k : 0u) | (a.wo_nan ? 1u << (16 + k) : 0u);
-#endif
                         if (a.need) {
-#if RS_SORT_STORE_RAY
                             F.cand_ray[wtile * (size_t)(kSortChunk * 64) + (size_t)(k * 64 + lane)] = f4(a.dir, a.tfar);
-#endif
                             const uint32_t rank = atomicAdd(&L.cur[a.bucket], 1u);
                             L.slot[k * 64 + lane] = a.pick | (rank << 21);
                             bkt[k >> 2] |= a.bucket << (8 * (k & 3));
@@ -951,7 +910,6 @@ __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst&
                     }
                 wave_lds_sync();
                 // ---- B: the chunk's shadow rays in bucket order (lane = ray)
-#if RS_SORT_STORE_RAY
                 if constexpr (trav_lane(T) && trav_wide(T)) {          // lanes refilled from the list (rs_scene.h)
                     occluded_wide_list(S, n_rays, FLT_MIN + F.tnear_off,
                         [&](uint32_t j, vec3& o, vec3& ld, float& tfar) {
@@ -967,34 +925,15 @@ __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst&
                             if (occ) atomicOr(&L.occ[sl & 63u], 1u << (sl >> 6));
                         });
                 } else
-#endif
                 for (uint32_t j0 = 0; j0 < n_rays; j0 += 64u) {
                     const uint32_t j = j0 + (uint32_t)lane;
                     const bool act = j < n_rays;
                     const uint32_t sl = L.e[act ? j : 0u];
-                    const uint32_t pick = L.slot[sl] & 0x1fffffu, k = sl >> 6, src = sl & 63u;
+                    const uint32_t k = sl >> 6, src = sl & 63u;
                     const vec3 o = mk(L.px[src], L.py[src], L.pz[src]);
-#if RS_SORT_STORE_RAY
-                    (void)pick;
                     const float4 dt = F.cand_ray[wtile * (size_t)(kSortChunk * 64) + sl];   // phase A's evaluate_f_pre ray
                     const vec3 ld = xyz(dt);
                     const float tfar = dt.w;
-#else
-                    Rng q;
-                    q.init(F.seed, F.frame, PASS_INITIAL,
-                           (uint32_t)(ty0 + (int)(src >> 3)) * (uint32_t)F.W + (uint32_t)(tx0 + (int)(src & 7u)));
-                    q.n = cand_slot(c0 + (int)k) + 1u;
-                    const float r1 = q.range(0, 1), r2 = q.range(0, 1);    // area_sample_at's draws
-                    const float4* E = S.emis + 8 * (size_t)pick;
-                    const vec3 p0 = xyz(E[0]), p1 = xyz(E[1]), p2 = xyz(E[2]);
-                    const float sr = sqrtf(r1);
-                    const float bx = 1.0f - sr, by = sr * (1.0f - r2), bz = sr * r2;
-                    const vec3 pt = (p0 * bx + p1 * by) + p2 * bz;
-                    vec3 ld = pt - o;                                        // evaluate_f_pre's ray
-                    const float r2s = dot(ld, ld);
-                    ld = normalize(ld);
-                    const float tfar = sqrtf(r2s) - F.tfar_off;
-#endif
                     const bool occ = trace_any<T>(S, act, o, ld, FLT_MIN + F.tnear_off, tfar);
                     rays += act ? 1u : 0u;
                     if (act && occ) atomicOr(&L.occ[src], 1u << k);
@@ -1002,7 +941,6 @@ __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst&
                 wave_lds_sync();
                 // ---- C: phase A's weights, the reservoir stream in candidate order (lane = pixel)
                 const uint32_t occm = L.occ[lane];
-#if RS_SORT_STORE_W
                 for (int k = 0; k < nk; ++k) {
                     const int c = c0 + k;
                     const bool use_u = ((flg >> k) & 1u) && !(((needm & occm) >> k) & 1u);
@@ -1010,18 +948,6 @@ __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst&
                     rng.n = cand_slot(c) + 3u;
                     if (alive && res_add_w(r, w, 0, rng)) sel = c;
                 }
-#else
-                const GElem g = G.load(p);
-                const ShadeFrame sf = make_frame(g, cam);
-                for (int k = 0; k < nk; ++k) {
-                    const int c = c0 + k;
-                    const AreaCand a = area_cand(S, F, g.pos, sf, rng, c, tv, alive, inv_ma);
-                    const bool use_u = a.ok && !(a.need && ((occm >> k) & 1u));
-                    const float w = use_u ? a.wu : (a.wo_nan ? __int_as_float(0x7fc00000) : 0.0f);
-                    rng.n = cand_slot(c) + 3u;
-                    if (alive && res_add_w(r, w, 0, rng)) sel = c;
-                }
-#endif
             }
             if (sel >= 0) {
                 const GElem g = G.load(p);
@@ -1036,7 +962,7 @@ __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst&
             // re-read around them, so only the sample in flight is live across a walk
             const float inv_mb = 1.0f / (float)F.m_brdf;
             for (int i = 0; i < F.m_brdf; ++i) {
-                if (RS_SORT_PARK) brdf_park(L.slot, lane, r, best_phat, f_sel);
+                brdf_park(L.slot, lane, r, best_phat, f_sel);
                 float Wc, mis;
                 rng.n = cand_slot(F.m_area + i);
                 Sample s;
@@ -1051,7 +977,7 @@ __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst&
                     f = evaluate_f<T>(S, F, s, g.pos, false, make_frame(g, cam), tv, alive, rays);
                 }
                 asm volatile("" ::: "memory");
-                if (RS_SORT_PARK) brdf_unpark(L.slot, lane, r, best_phat, f_sel);
+                brdf_unpark(L.slot, lane, r, best_phat, f_sel);
                 float ph = length(f);
                 float w = F.m_area > 0 ? mis * ph * Wc : inv_mb * ph * Wc;
                 rng.n = cand_slot(F.m_area + i) + 3u;
@@ -1086,7 +1012,7 @@ k_gbuffer_initial_sorted(DevScene S, FrameConst F, GBuf G, ResBuf Rw, float* fb,
     const int wave = threadIdx.x >> 6;
     const int tx0 = bx * 16 + (wave & 1) * 8, ty0 = F.gy0 + by * 16 + (wave >> 1) * 8;
     const size_t hslot = (size_t)((ty0 - F.gy0) >> 3) * (size_t)(2 * ((F.W + 15) >> 4)) + (size_t)(tx0 >> 3);   // the launch's 8x8 tile
-    sorted_tile<T>(S, F, G, Rw, fb, fuse_shade, lds[wave], threadIdx.x & 63, x, y, in, tx0, ty0, hslot, rays);
+    sorted_tile<T>(S, F, G, Rw, fb, fuse_shade, lds[wave], threadIdx.x & 63, x, y, in, hslot, rays);
     count_rays(C, rays + (in ? 1u : 0u), in ? 1u : 0u, t0, y);
 }
 // the same pass by persistent waves (RESTIR_PERSIST_SORTED): about one device's worth of resident workgroups,
@@ -1108,9 +1034,7 @@ k_gbuffer_initial_sorted_pq(DevScene S, FrameConst F, GBuf G, ResBuf Rw, float* 
         const uint64_t t0 = wave_clock();
         int x, y;
         const bool in = pixel_of_q(F, F.gy0, F.gy1, t, x, y);
-        int tx0, ty0;
-        tile_origin_q(F, F.gy0, F.gy1, t, tx0, ty0);
-        sorted_tile<T>(S, F, G, Rw, fb, fuse_shade, lds[wave], lane, x, y, in, tx0, ty0,
+        sorted_tile<T>(S, F, G, Rw, fb, fuse_shade, lds[wave], lane, x, y, in,
                        (size_t)blockIdx.x * 4 + (size_t)wave, rays);   // the resident wave's slot
         rays += in ? 1u : 0u;
         prim += in ? 1u : 0u;

@@ -141,9 +141,8 @@ __device__ __forceinline__ float4 sload(const float4* p, uint32_t i) {
     return p[i];   // host pass only type-checks device code
 #endif
 }
-// wave-uniform node load for the lockstep walks: scalar cache (default) or, with RS_NODE_VMEM, one
-// broadcast vector load through L1 (32 KB/CU) with the control words moved to SGPRs
-// (a broadcast vector load through L1 + readfirstlane was measured 10 % slower on C2)
+// wave-uniform node load for the lockstep walks, through the scalar cache (one broadcast vector load through
+// L1 + readfirstlane of the control words was measured 10 % slower on C2)
 __device__ __forceinline__ void node_load(const float4* nodes, uint32_t m, float4& a, float4& b) {
     a = sload(nodes, 2 * m); b = sload(nodes, 2 * m + 1);
 }

@@ -41,7 +41,7 @@ def wang(x):                # Thomas Wang's hash32shift (shifts and adds only; *
     return x
 
 
-def xorshift(x):            # the timing-only diagnostic (RS_DIAG_CHEAP_RNG): linear over GF(2)
+def xorshift(x):            # a timing-only stand-in once built for the cost of the hash: linear over GF(2)
     x = x.astype(np.uint64)
     x ^= (x << np.uint64(13)) & M32; x ^= x >> np.uint64(17); x ^= (x << np.uint64(5)) & M32; x ^= x >> np.uint64(16)
     return x
