@@ -121,6 +121,28 @@ public:
         }
         ++frameCtr;
     }
+    // SimpleGuiDX11::produceStandard(t) (pg/simpleguidx11.cpp:336-357) with the NEE path integrator
+    // (pg/NEEPathIntegrator.cpp:72-131, MIS direct integrator): one frame of samplesPerPixel paths per pixel
+    // under pathParams; frame_data() is this frame (the call waits for it), shadingPassDuration /
+    // totalFrameDuration the launch.  The ReSTIR history is untouched; frameCtr keys the RNG and advances.
+    void produceStandard(float t = 0.0f) {
+        (void)t;
+        if (!scene_) throw Error(RS_E_INVALID, "produceStandard: no scene loaded");
+        finish();
+        rs_pass_times pt{};
+        check(rs_render_path(ctx_, scene_, &camera_, &params, &pathParams, frameCtr, samplesPerPixel, ring_[cur_],
+                             timePasses ? &pt : nullptr), ctx_);
+        shown_ = ring_[cur_]; shown_frame_ = (long long)frameCtr;
+        cur_ = (cur_ + 1) % kRing;
+        if (timePasses) {
+            gBUfferFillDuration = initialCandidatesGenDuration = visibilityPassDuration = 0.0f;
+            temporalReusePassDuration = spatialReusePassDuration = bufferCopyDuration = 0.0f;
+            shadingPassDuration = pt.shade_ms;
+            totalFrameDuration = pt.total_ms;
+            raysTraced = pt.rays;
+        }
+        ++frameCtr;
+    }
     // pipelined mode: wait for the outstanding readbacks; frame_data() is then the last frame produced
     void finish() {
         while (n_pending_ > 0) publish();
@@ -161,6 +183,9 @@ public:
 
     Camera camera_;
     Params params;
+    // produceStandard: RenderParams::maxBounceCount, NaivePathIntegrator::RR, NEEPathIntegrator::calcDI / calcGI
+    rs_path_params pathParams{5, 1, 1, 1};
+    uint32_t samplesPerPixel = 1;
     uint32_t frameCtr = 0;
     int pipelineDepth = 0;
     bool timePasses = true;

@@ -217,6 +217,26 @@ int rs_render_frame(rs_context* ctx, const rs_scene* scene, const rs_camera* cam
 int rs_render_direct_mis(rs_context* ctx, const rs_scene* scene, const rs_camera* camera,
                          const rs_frame_params* params, uint32_t frame_index, uint32_t spp,
                          float* frame_rgb_host, rs_pass_times* times);
+/* ---- NEE path tracer: global-illumination ground truth ---------------------------------------- */
+/* The same integrator with calcGI on (SimpleGuiDX11::produceStandard, the reference's second render mode):
+ * at every path vertex the MIS direct estimate above plus one BRDF-sampled continuation ray, up to
+ * max_bounces bounces, Russian roulette on the material's max(Kd, Ks) component at bounce > 5; an emitter
+ * counts only at the camera vertex.  Material model of the MIS ground truth (Phong for PHONG/DIELECTRIC,
+ * Lambert otherwise; no mirror or transparent bounces).  With calc_gi = 0 the frame is
+ * rs_render_direct_mis's bit for bit.  Contract of rs_render_direct_mis: one launch on the context's stream,
+ * spp in [1, 65536] samples per pixel averaged into the framebuffer, ReSTIR history untouched, times
+ * (optional) reports the launch in shade_ms/total_ms and the rays traced; synchronises if times or
+ * frame_rgb_host is given.  RS_E_INVALID: null arguments, a scene of another context, a tile frame in
+ * flight, spp or max_bounces out of range; RS_E_UNSUPPORTED: use_skybox without a sky. */
+typedef struct {
+    int32_t max_bounces;       /* RenderParams::maxBounceCount (pg/RenderParams.h:8, default 5); 0..15 */
+    int32_t russian_roulette;  /* NaivePathIntegrator::RR (default true); acts only at bounce > 5 */
+    int32_t calc_di;           /* NEEPathIntegrator::calcDI (default true) */
+    int32_t calc_gi;           /* NEEPathIntegrator::calcGI (default true) */
+} rs_path_params;
+int rs_render_path(rs_context* ctx, const rs_scene* scene, const rs_camera* camera,
+                   const rs_frame_params* params, const rs_path_params* path, uint32_t frame_index,
+                   uint32_t spp, float* frame_rgb_host, rs_pass_times* times);
 
 /* Pass times and rays summed over every frame finished since context creation (or the last reset),
  * without a host sync per frame: each frame records into its own slot of an event ring and the rays

@@ -6,6 +6,7 @@
 // (pg/camera.cpp:12-84) and sequences the passes of produceRestir (pg/simpleguidx11.cpp:359-487).
 #include "rs_passes.h"
 #include "rs_mis.h"
+#include "rs_path.h"
 #include "rs_post.h"
 #include "rs_refit.h"
 #include "../../include/restir_c.h"
@@ -1983,16 +1984,20 @@ extern "C" int rs_render_frame(rs_context* c, const rs_scene* s, const rs_camera
     return RS_OK;
 }
 
-// MIS direct-light ground truth (rs_mis.h) into the framebuffer: one launch, spp
-// samples per pixel.  Does not touch the ReSTIR history (G-buffers, reservoirs, frame counter).
-extern "C" int rs_render_direct_mis(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
-                                    uint32_t frame_index, uint32_t spp, float* frame_rgb_host, rs_pass_times* t) {
-    if (!c || !s || !cam || !P) return fail(c, RS_E_INVALID, "rs_render_direct_mis: null argument");
-    if (s->ctx != c) return fail(c, RS_E_INVALID, "rs_render_direct_mis: scene belongs to another context");
-    if (c->active) return fail(c, RS_E_INVALID, "rs_render_direct_mis: a tile frame is in flight");
+// The ground-truth renders (rs_mis.h, rs_path.h) into the framebuffer: one launch on the context's stream, spp
+// samples per pixel.  Does not touch the ReSTIR history (G-buffers, reservoirs, frame counter).  launch(T, S, F,
+// grid, slot) enqueues the kernel of traversal kind T on c->fs and returns its hipError_t.
+template <class Launch>
+static int render_ground_truth(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                               uint32_t frame_index, uint32_t spp, float* frame_rgb_host, rs_pass_times* t,
+                               const char* who, Launch&& launch) {
+    const std::string fn = who;
+    if (!c || !s || !cam || !P) return fail(c, RS_E_INVALID, fn + ": null argument");
+    if (s->ctx != c) return fail(c, RS_E_INVALID, fn + ": scene belongs to another context");
+    if (c->active) return fail(c, RS_E_INVALID, fn + ": a tile frame is in flight");
     if (P->use_skybox && s->sky < 0)
         return fail(c, RS_E_UNSUPPORTED, "use_skybox: the scene has no sky map (rs_scene_set_sky / rs_scene_load_sky)");
-    if (spp < 1 || spp > 65536) return fail(c, RS_E_INVALID, "rs_render_direct_mis: spp must be in [1, 65536]");
+    if (spp < 1 || spp > 65536) return fail(c, RS_E_INVALID, fn + ": spp must be in [1, 65536]");
     HIPCHK(c, enter(c));
     FrameConst F = {};
     F.bg = vec3{P->bg_color[0], P->bg_color[1], P->bg_color[2]};
@@ -2018,8 +2023,7 @@ extern "C" int rs_render_direct_mis(rs_context* c, const rs_scene* s, const rs_c
     pick_traversal(c, s);
     c->twide = s->wide_on;
     c->tuning = false;               // the ReSTIR frames own the per-scene traversal tuning
-    with_trav(c, [&](auto T) { k_direct_mis<T()><<<g, 256, 0, c->fs>>>(S, F, (int)spp, c->fb, count_slot(c, g)); });
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, with_trav(c, [&](auto T) { return launch(T, S, F, g, count_slot(c, g)); }));
     HIPCHK(c, hipEventRecord(e1, c->stream));
     k_reduce_counts<<<kReduceBlocks, kReduceThreads, 0, c->stream>>>(c->d_part, c->part_used, c->d_red,
                                                                      (unsigned*)(c->d_red + kReduceBlocks), c->d_cnt, c->d_tot);
@@ -2039,6 +2043,38 @@ extern "C" int rs_render_direct_mis(rs_context* c, const rs_scene* s, const rs_c
         }
     }
     return RS_OK;
+}
+
+// MIS direct-light ground truth (rs_mis.h)
+extern "C" int rs_render_direct_mis(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                                    uint32_t frame_index, uint32_t spp, float* frame_rgb_host, rs_pass_times* t) {
+    return render_ground_truth(c, s, cam, P, frame_index, spp, frame_rgb_host, t, "rs_render_direct_mis",
+                               [&](auto T, const DevScene& S, const FrameConst& F, dim3 g, CountSlot slot) {
+        k_direct_mis<T()><<<g, 256, 0, c->fs>>>(S, F, (int)spp, c->fb, slot);
+        return hipGetLastError();
+    });
+}
+
+// NEE path tracer: the global-illumination ground truth (rs_path.h).  The vertex records of the paths in flight
+// take (max_bounces + 1) * 8 KiB of dynamic LDS per workgroup: 48 KiB at the default, 128 KiB at the cap.
+extern "C" int rs_render_path(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                              const rs_path_params* pp, uint32_t frame_index, uint32_t spp, float* frame_rgb_host,
+                              rs_pass_times* t) {
+    if (!pp) return fail(c, RS_E_INVALID, "rs_render_path: null argument");
+    if (pp->max_bounces < 0 || pp->max_bounces > 15)
+        return fail(c, RS_E_INVALID, "rs_render_path: max_bounces must be in [0, 15]");
+    const PathConst Q = {(int)spp, pp->max_bounces, pp->russian_roulette ? 1 : 0, pp->calc_di ? 1 : 0, pp->calc_gi ? 1 : 0};
+    const size_t lds = (size_t)(Q.max_bounces + 1) * kPathRec * kPathBlock * sizeof(float);
+    return render_ground_truth(c, s, cam, P, frame_index, spp, frame_rgb_host, t, "rs_render_path",
+                               [&](auto T, const DevScene& S, const FrameConst& F, dim3 g, CountSlot slot) {
+        if (lds > 64 * 1024) {       // beyond what a launch may ask for unannounced
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_path_nee<T()>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        k_path_nee<T()><<<g, kPathBlock, lds, c->fs>>>(S, F, Q, c->fb, slot);
+        return hipGetLastError();
+    });
 }
 
 extern "C" int rs_get_frame_device_ptr(rs_context* c, const float** dptr) {

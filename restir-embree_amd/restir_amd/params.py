@@ -66,6 +66,19 @@ def default_params(**kw) -> FrameParams:
     return p
 
 
+class PathParams(ctypes.Structure):
+    """``rs_path_params``: the knobs of the NEE path tracer (Renderer.render_path)."""
+    _fields_ = [
+        ("max_bounces", ctypes.c_int32),          # RenderParams::maxBounceCount (pg/RenderParams.h:8); 0..15
+        ("russian_roulette", ctypes.c_int32),     # NaivePathIntegrator::RR; acts only at bounce > 5
+        ("calc_di", ctypes.c_int32),              # NEEPathIntegrator::calcDI
+        ("calc_gi", ctypes.c_int32),              # NEEPathIntegrator::calcGI
+    ]
+
+    def __init__(self, max_bounces=5, russian_roulette=True, calc_di=True, calc_gi=True):
+        super().__init__(int(max_bounces), int(bool(russian_roulette)), int(bool(calc_di)), int(bool(calc_gi)))
+
+
 def metric_params(**kw) -> FrameParams:
     """BASELINE.json metric point / C2: A=32 area candidates, B=1 BRDF candidate, spatial k=4,
     P=1, R=30, CONSTANT MIS, cap 20, temporal off, visibility pass off."""

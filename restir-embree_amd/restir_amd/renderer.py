@@ -15,7 +15,7 @@ import os
 
 import numpy as np
 
-from .params import FrameParams
+from .params import FrameParams, PathParams
 
 PKG_DIR = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(PKG_DIR, "librestir_amd.so")
@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "rs_denoiser_check_weights", "rs_denoiser_create", "rs_denoiser_create_from_file", "rs_denoiser_info_get",
     "rs_denoiser_execute", "rs_denoise_frame", "rs_context_set_denoiser", "rs_denoiser_set_timing",
     "rs_denoiser_last_ms", "rs_denoiser_layer_ms", "rs_denoiser_get_scale", "rs_denoiser_dump", "rs_denoiser_destroy",
+    "rs_render_path",
 ]
 
 # BVH traversal kinds (include/restir_c.h RS_TRAVERSAL_*)
@@ -203,6 +204,8 @@ def load_library(path: str = LIB_PATH):
                                   ctypes.POINTER(i32), vp, ctypes.c_size_t]
     L.rs_render_direct_mis.argtypes = [vp, vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(FrameParams), u32, u32, fp,
                                        ctypes.POINTER(PassTimes)]
+    L.rs_render_path.argtypes = [vp, vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(FrameParams),
+                                 ctypes.POINTER(PathParams), u32, u32, fp, ctypes.POINTER(PassTimes)]
     L.rs_frame_readback.argtypes = [vp, fp, ctypes.POINTER(ctypes.c_uint64)]
     L.rs_frame_wait.argtypes = [vp, ctypes.c_uint64]
     L.rs_host_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
@@ -600,6 +603,21 @@ class Renderer:
         self._check(self.lib.rs_render_direct_mis(self.h, scene.h, ctypes.byref(cam), ctypes.byref(params),
                                                   int(frame_index), int(spp), out,
                                                   ctypes.byref(self.last_times) if timed else None))
+        return self.frame_data if copy_out else None
+
+    def render_path(self, scene: Scene, camera, params: FrameParams, frame_index: int = 0, spp: int = 1,
+                    max_bounces: int = 5, russian_roulette: bool = True, calc_di: bool = True, calc_gi: bool = True,
+                    copy_out: bool = True, timed: bool = False) -> np.ndarray | None:
+        """NEE path tracer (rs_render_path; NEEPathIntegrator::integrateImpl2 with the MIS direct integrator):
+        direct plus indirect light up to max_bounces, spp samples per pixel into the framebuffer.  calc_gi=False
+        is render_direct_mis bit for bit.  Accumulate frames with post_frame(accumulate=True).  timed=True fills
+        last_times (shade_ms = the launch, rays)."""
+        cam = camera_desc(camera)
+        pp = PathParams(max_bounces, russian_roulette, calc_di, calc_gi)
+        out = self.frame_data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if copy_out else None
+        self._check(self.lib.rs_render_path(self.h, scene.h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(pp),
+                                            int(frame_index), int(spp), out,
+                                            ctypes.byref(self.last_times) if timed else None))
         return self.frame_data if copy_out else None
 
     def debug_trace(self, scene: Scene, o, d, tnear, tfar, any_hit: bool, lockstep: bool = True,

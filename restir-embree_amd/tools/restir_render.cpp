@@ -6,6 +6,9 @@
 //   restir_render [--obj file.obj] [--w 1920 --h 1080] [--frames 10] [--area 32] [--brdf 1]
 //                 [--spatial k] [--temporal] [--out frame.pfm] [--eye x y z --at x y z --fov deg]
 //                 [--bench] [--ranks N [--compare]] [--denoise weights.tza [--png display.png]]
+//                 [--path SPP [--bounces N]]
+// --path SPP: the frames are produceStandard's instead -- the NEE path tracer (direct + indirect light up to N
+// bounces, default 5) at SPP samples per pixel, accumulated like the ReSTIR frames; --out writes the last.
 // --bench: the drop-in throughput -- frames/s of produceRestir with frame_data landing in host memory
 // every frame, pipelined (pipelineDepth 2 and 1: readbacks overlapping the next frames, timePasses off)
 // and with the reference's synchronous semantics; one JSON line.
@@ -41,7 +44,7 @@ int main(int argc, char** argv) {
     std::string obj, out, denoise_w, png;
     int W = 512, H = 512, frames = 5;
     bool bench = false, cam_set = false, compare = false;
-    int ranks = 0;
+    int ranks = 0, path_spp = 0, bounces = 5;
     float eye[3] = {0, 0, 0}, at[3] = {0, 0, 0}, fov = 40.0f;
     restir::Renderer* rp = nullptr;
     restir::Params prm;
@@ -62,6 +65,8 @@ int main(int argc, char** argv) {
         else if (a == "--compare") compare = true;
         else if (a == "--denoise") denoise_w = next();
         else if (a == "--png") png = next();
+        else if (a == "--path") path_spp = std::atoi(next());
+        else if (a == "--bounces") bounces = std::atoi(next());
         else if (a == "--eye") { for (float& v : eye) v = (float)std::atof(next()); cam_set = true; }
         else if (a == "--at") { for (float& v : at) v = (float)std::atof(next()); cam_set = true; }
         else if (a == "--fov") fov = (float)std::atof(next());
@@ -156,7 +161,17 @@ int main(int argc, char** argv) {
             r.initOIDN(denoise_w);
             r.denoise = true;
         }
+        r.samplesPerPixel = (uint32_t)path_spp;
+        r.pathParams.max_bounces = bounces;
         for (int f = 0; f < frames; ++f) {
+            if (path_spp > 0) {
+                r.produceStandard();
+                r.postFrame();
+                std::printf("frame %d: path tracer %u spp, %d bounces: %.3f ms, rays %llu, accumulator mean %.6f "
+                            "var %.6f (%u frames)\n", f, r.samplesPerPixel, bounces, r.totalFrameDuration,
+                            (unsigned long long)r.raysTraced, r.accumulatorMean, r.accumulatorVariance, r.accFrameCtr);
+                continue;
+            }
             r.produceRestir();
             r.postFrame();
             std::printf("frame %d: gbuffer+initial %.3f ms, temporal %.3f ms, spatial %.3f ms, shade %.3f ms, "

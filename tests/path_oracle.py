@@ -1,0 +1,112 @@
+"""ctypes wrapper for the path-tracer checker (tests/cpp/path_oracle.c: or_render_path over the oracle's own
+statics).  TEST INFRASTRUCTURE ONLY.
+
+The file includes oracle/restir_oracle.c and is compiled on demand with exactly the flags of oracle/Makefile, so
+scene and context handles made by oracle_lib (same source, same flags, same layouts) may be passed to it.  Also
+holds the integrating-sphere scene the CPU and GPU tests share, with its closed form.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+import subprocess
+
+import numpy as np
+
+import oracle_lib as O
+from restir_amd import scenes
+from restir_amd.params import FrameParams, PathParams
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "cpp", "path_oracle.c")
+DEPS = [SRC, os.path.join(ROOT, "oracle", "restir_oracle.c"), os.path.join(ROOT, "restir-embree_amd", "csrc", "rs_libm.h")]
+SO = os.path.join(ROOT, "oracle", "_build", "libpath_oracle.so")
+CFLAGS = "-O2 -std=c11 -fPIC -fopenmp -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function".split()   # oracle/Makefile
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        os.makedirs(os.path.dirname(SO), exist_ok=True)
+        if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in DEPS):
+            subprocess.check_call([os.environ.get("CC", "gcc"), *CFLAGS, "-shared", "-o", SO, SRC, "-lm"])
+        L = ctypes.CDLL(SO)
+        L.or_render_path.restype = ctypes.c_int
+        L.or_render_path.argtypes = [ctypes.c_void_p, ctypes.c_void_p, O._f32p, ctypes.POINTER(FrameParams),
+                                     ctypes.POINTER(PathParams), ctypes.c_uint32, ctypes.c_int, O._f32p,
+                                     ctypes.POINTER(ctypes.c_uint64)]
+        _lib = L
+    return _lib
+
+
+def render_path(orenderer, oscene, camera, params, frame_index=0, spp=1, max_bounces=5, russian_roulette=True,
+                calc_di=True, calc_gi=True):
+    """or_render_path on an oracle_lib.OracleRenderer / OracleScene pair: one (H, W, 3) frame; .rays on the renderer."""
+    cam = np.ascontiguousarray(camera.as_array() if hasattr(camera, "as_array") else camera, np.float32)
+    out = np.zeros((orenderer.H, orenderer.W, 3), np.float32)
+    rays = ctypes.c_uint64()
+    pp = PathParams(max_bounces, russian_roulette, calc_di, calc_gi)
+    rc = lib().or_render_path(orenderer.h, oscene.h, O._ptr(cam), ctypes.byref(params), ctypes.byref(pp), frame_index,
+                              spp, O._ptr(out), ctypes.byref(rays))
+    if rc != 0:
+        raise RuntimeError(f"or_render_path failed: {rc}")
+    orenderer.rays = int(rays.value)
+    return out
+
+
+# ---------------------------------------------------------------- integrating sphere
+SPHERE_KD, SPHERE_LE, SPHERE_W, SPHERE_H = 0.5, 10.0, 32, 24
+
+
+def _icosphere(subdiv):
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t),
+         (t, 0, -1), (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]
+    v = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in v]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+         (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7),
+         (9, 8, 1)]
+    for _ in range(subdiv):
+        mid, nf = {}, []
+
+        def m(a, b):
+            k = (min(a, b), max(a, b))
+            if k not in mid:
+                p = v[a] + v[b]
+                v.append(p / np.linalg.norm(p))
+                mid[k] = len(v) - 1
+            return mid[k]
+
+        for a, b, c in f:
+            ab, bc, ca = m(a, b), m(b, c), m(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    return np.asarray(v), np.asarray(f)
+
+
+def integrating_sphere():
+    """(scene, f): a unit icosphere of 3 subdivisions (1280 triangles) seen from inside, vertex normals = -position,
+    Lambert kd 0.5; the triangles whose centroid has z > 0.9 emit Le = 10; f = emitter area / mesh area."""
+    v, f = _icosphere(3)
+    tri = v[f]                                               # (T, 3, 3)
+    emit = tri.mean(axis=1)[:, 2] > 0.9
+    area = 0.5 * np.linalg.norm(np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]), axis=1)
+    pos = tri.reshape(-1, 9).astype(np.float32)
+    mats = [scenes.Material(kd=(SPHERE_KD,) * 3, type=scenes.LAMBERT), scenes.Material(le=(SPHERE_LE,) * 3, type=scenes.LAMBERT)]
+    sc = scenes.Scene(positions=np.ascontiguousarray(pos), normals=np.ascontiguousarray(-pos),
+                      tri_material=np.ascontiguousarray(emit.astype(np.uint32)), materials=mats,
+                      camera=scenes.Camera(eye=(0.0, 0.0, 0.0), at=(0.0, 1.0, -0.3), fov_y=60.0), name="integrating_sphere")
+    return sc, float(area[emit].sum() / area.sum())
+
+
+def sphere_expected(f, m):
+    """Every Lambertian patch of a sphere irradiates every point equally, so the radiance leaving a non-emitting
+    point after m bounces is kd Le f sum_{j<=m} (kd (1 - f))^j."""
+    return SPHERE_KD * SPHERE_LE * f * sum((SPHERE_KD * (1.0 - f)) ** j for j in range(m + 1))
+
+
+def sphere_measure(render):
+    """render(frame) -> (H, W, 3) at 64 spp; mean red of frames 0-3 over the pixels that do not see the emitter."""
+    img = np.mean([render(fr).astype(np.float64) for fr in range(4)], axis=0)[..., 0]
+    return float(img[img < 9.9].mean())
