@@ -1568,10 +1568,24 @@ k_spatial(DevScene S, FrameConst F, GBuf G, ResBuf Rr, ResBuf Rw, int pass_idx, 
         float rcpM = M > 0 ? 1.0f / (float)M : 0.0f;
         vec3 f_sel = mk(0, 0, 0);
         if (mode == MIS_CONSTANT) {
-            // CONSTANT MIS (the metric point): the k+1 candidates' shadow rays all start at this pixel,
-            // so pairs share one walk (trace_any_multi); the addSample draws stay in candidate order
+            // CONSTANT MIS (the metric point): the candidates' shadow rays all start at this pixel, so pairs
+            // share one walk (trace_any_multi); the addSample draws stay in candidate order 0, 1, 2, ...
             const ShadeFrame sf = make_frame(th, cam);
-            for (int i0 = 0; i0 < kk; i0 += 2) {
+            int i0 = 0;
+            if (F.canon_vis) {                             // wave-uniform
+                // list position 0 is the pixel's own sample, known unoccluded (f = L as traced): it
+                // has no ray, so it goes first without a walk and the neighbours fill whole pairs (1,2), (3,4),
+                // ...: k = 4 takes two walks, not the three of (0,1), (2,3), (4,-).  After a visibility pass the
+                // first spatial pass traces it, paired as (0,1), (2,3), ...
+                const Res r0 = Rr.load(p);
+                FPre pre0 = evaluate_f_pre(F, smp_of(r0), th.pos, false, sf, true, alive);
+                pre0.need = false;
+                const vec3 f = evaluate_f_post(pre0, false);
+                const float rw = rcpM * length(f) * r0.W;
+                if (alive && res_add(res, smp_of(r0), rw, r0.conf, rng)) { sel = 0; f_sel = f; }
+                i0 = 1;
+            }
+            for (; i0 < kk; i0 += 2) {
                 FPre pre[2];
                 Res rr[2];
                 bool act[2], occ[2];
@@ -1582,7 +1596,6 @@ k_spatial(DevScene S, FrameConst F, GBuf G, ResBuf Rr, ResBuf Rw, int pass_idx, 
                     const int i = i0 + k;
                     rr[k] = Rr.load(list_q(i));
                     pre[k] = evaluate_f_pre(F, smp_of(rr[k]), th.pos, false, sf, true, alive && i < cnt);
-                    pre[k].need = pre[k].need && !(i == 0 && F.canon_vis);   // known unoccluded: f = L as traced
                     act[k] = pre[k].need; dir[k] = pre[k].dir; tf[k] = pre[k].tfar; occ[k] = false;
                     rays += act[k] ? 1u : 0u;
                 }
