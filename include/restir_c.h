@@ -531,6 +531,14 @@ int rs_debug_trace(rs_context* ctx, const rs_scene* scene, uint32_t n, const flo
 int rs_debug_wide_tree(const rs_scene* scene, uint32_t* n_nodes, uint32_t* n_tris, int32_t* depth, uint32_t* words,
                        int32_t* prims);
 
+/* ---- test hook: the scene's binary skip-pointer tree (what every lockstep walk, and every per-lane walk of a
+ * scene without an 8-wide tree, follows; built by rs_bvh_build.hip, refit in place with the positions) ---------
+ * *n_nodes / *n_tris = its size.  With nodes != NULL (8 * *n_nodes floats) it copies the scene's current node
+ * records -- lo.xyz, skip (int bits), hi.xyz, leaf word (int bits: -1 interior, else (first << 3) | (count - 1))
+ * -- and with prims != NULL (*n_tris int32) each leaf-order triangle slot's original triangle index.  It waits
+ * for a pipelined rs_scene_update_positions and synchronises. */
+int rs_debug_bvh_tree(const rs_scene* scene, uint32_t* n_nodes, uint32_t* n_tris, float* nodes, int32_t* prims);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1140,7 +1140,8 @@ extern "C" int rs_scene_update_positions(rs_scene* s, const float* positions, co
     if (pipelined) {                             // later frames read the new copy
         std::swap(s->d_nodes, s->a_nodes); std::swap(s->d_tris, s->a_tris); std::swap(s->d_emis, s->a_emis);
         std::swap(s->d_cdf, s->a_cdf); std::swap(s->d_cdf_guide, s->a_cdf_guide);
-        std::swap(s->wide, s->a_wide);
+        // (a scene without a live wide tree has no second copy: s->wide keeps the reason, rs_scene_walk_info)
+        if (s->wide_on) std::swap(s->wide, s->a_wide);
         s->gen++;
     }
     return RS_OK;
@@ -1311,6 +1312,27 @@ extern "C" int rs_debug_wide_tree(const rs_scene* s, uint32_t* n_nodes, uint32_t
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (prims)
         for (uint32_t k = 0; k < w.n_tris; ++k) std::memcpy(&prims[k], &t[3 * (size_t)k].w, 4);
+    return RS_OK;
+}
+
+extern "C" int rs_debug_bvh_tree(const rs_scene* s, uint32_t* n_nodes, uint32_t* n_tris, float* nodes, int32_t* prims) {
+    if (!s || !n_nodes || !n_tris) return fail(s ? s->ctx : nullptr, RS_E_INVALID, "rs_debug_bvh_tree: null argument");
+    rs_context* c = s->ctx;
+    HIPCHK(c, enter(c));
+    const bool on = s->d_nodes && s->d_tris && s->n_nodes;
+    *n_nodes = on ? s->n_nodes : 0u;
+    *n_tris = on ? s->n_tris : 0u;
+    if (!on || (!nodes && !prims)) return RS_OK;
+    if (s->update_recorded) HIPCHK(c, hipStreamWaitEvent(c->stream, s->update_ev, 0));   // a pipelined update
+    if (nodes) HIPCHK(c, hipMemcpyAsync(nodes, s->d_nodes, (size_t)s->n_nodes * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    std::vector<float4> t;
+    if (prims) {
+        t.resize(3 * (size_t)s->n_tris);
+        HIPCHK(c, hipMemcpyAsync(t.data(), s->d_tris, t.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (prims)
+        for (uint32_t k = 0; k < s->n_tris; ++k) std::memcpy(&prims[k], &t[3 * (size_t)k].w, 4);
     return RS_OK;
 }
 

@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = [
     "rs_denoiser_check_weights", "rs_denoiser_create", "rs_denoiser_create_from_file", "rs_denoiser_info_get",
     "rs_denoiser_execute", "rs_denoise_frame", "rs_context_set_denoiser", "rs_denoiser_set_timing",
     "rs_denoiser_last_ms", "rs_denoiser_layer_ms", "rs_denoiser_get_scale", "rs_denoiser_dump", "rs_denoiser_destroy",
-    "rs_render_path",
+    "rs_render_path", "rs_debug_bvh_tree",
 ]
 
 # BVH traversal kinds (include/restir_c.h RS_TRAVERSAL_*)
@@ -174,6 +174,8 @@ def load_library(path: str = LIB_PATH):
     L.rs_tile_finish.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(PassTimes)]
     L.rs_debug_trace.argtypes = [vp, vp, u32, fp, fp, fp, fp, i32, fp, ctypes.POINTER(ctypes.c_int32)]
     L.rs_debug_wide_tree.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_int32), vp, vp]
+    if hasattr(L, "rs_debug_bvh_tree"):          # (absent from earlier builds, which A/Bs load)
+        L.rs_debug_bvh_tree.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), vp, vp]
     L.rs_scene_walk_info.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.rs_context_set_traversal.argtypes = [vp, i32]
     ip = ctypes.POINTER(ctypes.c_int32)
@@ -364,6 +366,19 @@ class Scene:
         r._check(r.lib.rs_debug_wide_tree(self.h, ctypes.byref(nn), ctypes.byref(nt), ctypes.byref(dp),
                                           words.ctypes.data_as(ctypes.c_void_p), prims.ctypes.data_as(ctypes.c_void_p)))
         return words, prims, dp.value
+
+    def bvh_tree(self):
+        """Test hook (rs_debug_bvh_tree): the scene's binary skip-pointer tree as (nodes (n_nodes, 8) float32 --
+        lo.xyz, skip, hi.xyz, leaf word; view columns 3 and 7 as int32 --, leaf-order triangle ids int32)."""
+        r = self.renderer
+        nn, nt = ctypes.c_uint32(), ctypes.c_uint32()
+        r._check(r.lib.rs_debug_bvh_tree(self.h, ctypes.byref(nn), ctypes.byref(nt), None, None))
+        nodes = np.zeros((nn.value, 8), np.float32)
+        prims = np.zeros(nt.value, np.int32)
+        if nn.value:
+            r._check(r.lib.rs_debug_bvh_tree(self.h, ctypes.byref(nn), ctypes.byref(nt),
+                                             nodes.ctypes.data_as(ctypes.c_void_p), prims.ctypes.data_as(ctypes.c_void_p)))
+        return nodes, prims
 
     def close(self):
         if self.h:
