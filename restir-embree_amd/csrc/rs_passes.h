@@ -47,8 +47,9 @@
 #define RS_TEMPORAL_WAVES_LANE 5
 #endif
 #define RS_WAVES(T, lockstep, lane) (((T) & TRAV_LANE) ? (lane) : (lockstep))
-// area candidates whose shadow rays share one lockstep traversal (occluded_wave_multi); 4 measured on
-// C2 1080p: 694-698 frames/s at a 4-wave budget (700-704 with 2), 560 at 5 waves (register spills)
+// area candidates whose shadow rays share one lockstep traversal (occluded_wave_multi) in the candidate-split pass
+// (k_gbuffer_initial_split).  One ray per walk is 11 % slower than two; the one-thread-per-pixel pass
+// takes three (RS_RIS_BATCH_PIXEL)
 #ifndef RS_RIS_BATCH
 #define RS_RIS_BATCH 2
 #endif
@@ -56,6 +57,10 @@
 // second pending ray is register pressure inside the walk loop: C3 +1.3 %)
 #ifndef RS_RIS_BATCH_LANE
 #define RS_RIS_BATCH_LANE 1
+#endif
+// ... for the lockstep kinds of the one-thread-per-pixel initial pass (k_gbuffer_initial): three
+#ifndef RS_RIS_BATCH_PIXEL
+#define RS_RIS_BATCH_PIXEL 3
 #endif
 
 namespace rs {
@@ -322,6 +327,7 @@ __device__ __forceinline__ GElem gbuffer_fill(const DevScene& S, const FrameCons
 // a workgroup's copy of them in LDS (LightLds, below).  Both hold the same values and the search makes the
 // same comparisons, so the index is the same bit for bit.
 struct LightGlobal {
+    static constexpr bool kLds = false;
     const float* cdf_g;
     const int* guide_g;
     __device__ __forceinline__ explicit LightGlobal(const DevScene& S) : cdf_g(S.cdf), guide_g(S.cdf_guide) {}
@@ -355,6 +361,7 @@ static_assert(kLightLdsMax % 4 == 0 && kLightLdsMax / 4 == 2 * 256 && kCdfGuide 
               "LightFill: a 256-thread workgroup moves the CDF as 2 and the guide as 1 16-B load per thread");
 constexpr int LIGHT_LDS = 8;              // kernel template bit (beside Trav's): the light tables from LDS
 struct LightLds {
+    static constexpr bool kLds = true;
     const float* cdf_l;                   // __shared__ float[kLightLdsMax]
     const uint16_t* guide_l;              // __shared__ uint16_t[kCdfGuide + 1] (padded to 8 B)
     __device__ __forceinline__ float cdf(uint32_t i) const { return cdf_l[i]; }
@@ -548,6 +555,48 @@ __device__ __forceinline__ void area_batch(const DevScene& S, const FrameConst& 
 #pragma unroll
     for (int k = 0; k < kB; ++k) w_out[k] = (okb[k] && !(act[k] && occ[k])) ? wu[k] : wo[k];   // evaluate_f_post
 }
+// area_batch for the lockstep kinds of the one-thread-per-pixel initial pass: kA area candidates from c0 and, with
+// kR = 1, one more ray from the same point that rides in the walk's last slot (`ride`: the first BRDF candidate's
+// shadow ray, already counted; its occlusion comes back in ride_occ).  The candidates' ok / need flags and the
+// walk's answer are bit-sets in one register each (trace_any_bits), not three lane masks per candidate, and the
+// walk keeps one far bound per ray.  A candidate's weight is area_batch's bit for bit: an occluded ray was needed,
+// so `ok and not (need and occluded)` is `ok and not occluded`.
+template <int T, int kA, int kR>
+__device__ __forceinline__ void area_batch_px(const DevScene& S, const FrameConst& F, vec3 pos, const ShadeFrame& sf,
+                                              Rng& rng, int c0, int c_end, bool alive, bool tv, const uint32_t* pick,
+                                              float* w_out, uint32_t& rays, const FPre& ride, bool& ride_occ) {
+    float wu[kA], wo[kA];
+    uint32_t need = 0u, ok = 0u;
+    vec3 dir[kA + kR];
+    float tf[kA + kR];
+    const float inv_ma = 1.0f / (float)F.m_area;
+#pragma unroll
+    for (int k = 0; k < kA; ++k) {
+        float Wc, mis;
+        rng.n = cand_slot(c0 + k) + 1u;                 // slot +0 was the pick (area_pick)
+        const Sample s = area_sample_at(S, F, pos, sf, rng, pick[k], Wc, mis);
+        const FPre p = evaluate_f_pre(F, s, pos, false, sf, tv, alive && c0 + k < c_end);
+        const float ph = length(p.L);
+        const float m = F.m_brdf > 0 ? mis : inv_ma;
+        wu[k] = m * ph * Wc;
+        wo[k] = m * 0.0f * Wc;
+        need |= p.need ? 1u << k : 0u;
+        ok |= p.ok ? 1u << k : 0u;
+        dir[k] = p.dir; tf[k] = p.tfar;
+        rays += p.need ? 1u : 0u;
+        __builtin_amdgcn_sched_barrier(0);             // one candidate after the other: interleaved, the three spill
+    }
+    if (kR) {
+        need |= ride.need ? 1u << kA : 0u;
+        dir[kA] = ride.dir; tf[kA] = ride.tfar;
+    }
+    uint32_t occ = 0u;
+    if (tv) occ = trace_any_bits<T, kA + kR>(S, need, pos, dir, FLT_MIN + F.tnear_off, tf);
+    const uint32_t lit = ok & ~occ;
+#pragma unroll
+    for (int k = 0; k < kA; ++k) w_out[k] = ((lit >> k) & 1u) ? wu[k] : wo[k];   // evaluate_f_post
+    ride_occ = (occ >> kA) & 1u;
+}
 // the selected area candidate's sample and (unoccluded) f, re-drawn from its RNG slots (the pick through the
 // same table source L as the first draw's)
 template <class LT>
@@ -576,7 +625,17 @@ __device__ __forceinline__ Res initial_ris(const LT& L, const DevScene& S, const
     if (__ballot(alive) == 0) return r;                                 // wave-uniform exit
     Rng rng; rng.init(F.seed, F.frame, PASS_INITIAL, pix);
     const bool tv = !F.do_vis_pass;
-    constexpr int kB = trav_lane(T) ? RS_RIS_BATCH_LANE : RS_RIS_BATCH;
+    constexpr bool kLane = trav_lane(T);
+    constexpr int kB = kLane ? RS_RIS_BATCH_LANE : RS_RIS_BATCH_PIXEL;
+    // the next batch's picks in flight during the walk: a chain of global gathers, or the per-lane kind's one pick;
+    // picks from LDS answer in tens of cycles and are made when the batch needs them (kB registers less in the walk)
+    constexpr bool kAhead = kLane || !LT::kLds;
+    // The first BRDF candidate's shadow ray rides in the last area batch's walk when that batch has a free slot
+    // (lockstep kinds, rays traced in this pass): that batch is peeled, the candidate drawn in front of it.
+    const bool ride = !kLane && tv && F.m_brdf > 0 && F.m_area % kB != 0;       // wave-uniform
+    const int a_loop = ride ? F.m_area - F.m_area % kB : F.m_area;               // area candidates of the full batches
+    const FPre no_ride{};
+    bool ride_occ = false;
     float best_phat = 0.0f;
     if (F.m_area > 0) {
         // area candidates in batches of kB (area_batch: one walk per batch), then the reservoir updates
@@ -584,16 +643,32 @@ __device__ __forceinline__ Res initial_ris(const LT& L, const DevScene& S, const
         // instead of being carried per candidate (a selected candidate has w > 0: unoccluded, f = L).
         int sel = -1;
         uint32_t pick[kB];
+        if constexpr (kAhead) {
 #pragma unroll
-        for (int k = 0; k < kB; ++k) pick[k] = area_pick(L, S, rng, k);
-        for (int c0 = 0; c0 < F.m_area; c0 += kB) {
+            for (int k = 0; k < kB; ++k) pick[k] = area_pick(L, S, rng, k);
+        }
+        // without rays in the pass (a visibility pass follows) there is no walk to share: the lockstep kinds then take
+        // one candidate at a time, which keeps a batch's state out of the candidates' arithmetic
+        for (int c = 0; !kLane && !tv && c < F.m_area; ++c) {
+            if constexpr (!kLane) {
+                float w;
+                pick[0] = area_pick(L, S, rng, c);
+                area_batch_px<T, 1, 0>(S, F, pos, fs.load(), rng, c, F.m_area, alive, tv, pick, &w, rays, no_ride, ride_occ);
+                rng.n = cand_slot(c) + 3u;
+                if (alive && res_add_w(r, w, 0, rng)) sel = c;
+            }
+        }
+        for (int c0 = 0; (kLane || tv) && c0 < a_loop; c0 += kB) {
             float w[kB];
             uint32_t next[kB];
 #pragma unroll
-            for (int k = 0; k < kB; ++k) next[k] = area_pick(L, S, rng, c0 + kB + k);   // in flight during the walk
-            area_batch<T, kB>(S, F, pos, fs.load(), rng, c0, F.m_area, alive, tv, pick, w, rays);
+            for (int k = 0; k < kB; ++k) (kAhead ? next[k] : pick[k]) = area_pick(L, S, rng, c0 + (kAhead ? kB : 0) + k);
+            if constexpr (kLane) area_batch<T, kB>(S, F, pos, fs.load(), rng, c0, F.m_area, alive, tv, pick, w, rays);
+            else area_batch_px<T, kB, 0>(S, F, pos, fs.load(), rng, c0, F.m_area, alive, tv, pick, w, rays, no_ride, ride_occ);
+            if constexpr (kAhead) {
 #pragma unroll
-            for (int k = 0; k < kB; ++k) pick[k] = next[k];
+                for (int k = 0; k < kB; ++k) pick[k] = next[k];
+            }
 #pragma unroll
             for (int k = 0; k < kB; ++k) {
                 if (c0 + k < F.m_area) {
@@ -602,7 +677,43 @@ __device__ __forceinline__ Res initial_ris(const LT& L, const DevScene& S, const
                 }
             }
         }
-        if (sel >= 0) {
+        if constexpr (!kLane) {
+            if (ride) {
+                // BRDF candidate 0 up to its shadow ray (brdf_sample, evaluate_f's first half), the last kB - 1 or
+                // fewer area candidates with that ray in their walk, then the updates in candidate order as ever
+                float Wc, mis, w[kB - 1];
+                const ShadeFrame sf = fs.load();
+                rng.n = cand_slot(F.m_area);
+                const Sample s = brdf_sample<T>(S, F, pos, sf, alive, rng, Wc, mis, rays);
+                const FPre p = evaluate_f_pre(F, s, pos, false, sf, tv, alive);
+                rays += p.need ? 1u : 0u;
+                if constexpr (!kAhead) {
+#pragma unroll
+                    for (int k = 0; k < kB - 1; ++k) pick[k] = area_pick(L, S, rng, a_loop + k);
+                }
+                area_batch_px<T, kB - 1, 1>(S, F, pos, sf, rng, a_loop, F.m_area, alive, tv, pick, w, rays, p, ride_occ);
+#pragma unroll
+                for (int k = 0; k < kB - 1; ++k) {
+                    if (a_loop + k < F.m_area) {
+                        rng.n = cand_slot(a_loop + k) + 3u;
+                        if (alive && res_add_w(r, w[k], 0, rng)) sel = a_loop + k;
+                    }
+                }
+                if (sel >= 0) {
+                    const Sample sa = area_redraw(L, S, F, pos, fs.load(), rng, sel, tv, f_sel);
+                    best_phat = length(f_sel);
+                    r.p = sa.p; r.n = sa.n; r.li = sa.li;
+                }
+                const vec3 f = evaluate_f_post(p, ride_occ);
+                const float ph = length(f);
+                rng.n = cand_slot(F.m_area) + 3u;
+                if (alive && res_add(r, s, mis * ph * Wc, 0, rng)) { best_phat = ph; f_sel = f; }
+            } else if (sel >= 0) {
+                const Sample s = area_redraw(L, S, F, pos, fs.load(), rng, sel, tv, f_sel);
+                best_phat = length(f_sel);
+                r.p = s.p; r.n = s.n; r.li = s.li;
+            }
+        } else if (sel >= 0) {
             const Sample s = area_redraw(L, S, F, pos, fs.load(), rng, sel, tv, f_sel);
             best_phat = length(f_sel);
             r.p = s.p; r.n = s.n; r.li = s.li;
@@ -610,7 +721,7 @@ __device__ __forceinline__ Res initial_ris(const LT& L, const DevScene& S, const
     }
     if (F.m_brdf > 0) {
         float inv_mb = 1.0f / (float)F.m_brdf;
-        for (int i = 0; i < F.m_brdf; ++i) {
+        for (int i = ride ? 1 : 0; i < F.m_brdf; ++i) {
             float Wc, mis;
             rng.n = cand_slot(F.m_area + i);
             const ShadeFrame sf = fs.load();

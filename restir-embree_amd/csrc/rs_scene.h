@@ -18,6 +18,7 @@
 #pragma once
 #include "rs_device.h"
 #include "rs_lockstep.h"
+#include <type_traits>
 
 namespace rs {
 
@@ -570,9 +571,16 @@ __device__ __forceinline__ bool lockstep_enter(uint32_t& cur, uint32_t m, uint32
 // K any-hit rays per lane sharing one origin (a pixel's shadow rays to K light samples), one lockstep
 // walk: each lane keeps K cursors, the wave steps through the union of all 64*K paths; each step's node
 // (and leaf triangles) is loaded once and tested against every ray whose cursor is on it.
-template <int K>
-__device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const bool* active, vec3 o, const vec3* d,
-                                                    float tnear, const float* tfar, bool* occ) {
+// The rays with a ray (`active`) and the occluded ones (`occ`) are one bool per ray, or bit-sets (bit k = ray k):
+// ray_on reads either, the walk's end writes either.
+__device__ __forceinline__ bool ray_on(const bool* active, int k) { return active[k]; }
+__device__ __forceinline__ bool ray_on(uint32_t active, int k) { return (active >> k) & 1u; }
+// kOneBound: the leaf's triangle tests take the canonicalised bounds of the box tests instead of tnear / tfar
+// themselves, so a ray has one far bound live in the loop, not two -- walk_bound changes nothing but a signalling
+// NaN's quiet bit, and every comparison against a NaN is false either way.
+template <int K, bool kOneBound, class A, class O>
+__device__ __forceinline__ void occluded_wave_multi(const DevScene& S, A active, vec3 o, const vec3* d, float tnear,
+                                                    const float* tfar, O& occ) {
     vec3 inv[K];
     uint32_t cur[K];
     float tfar_c[K];
@@ -581,10 +589,9 @@ __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const boo
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         inv[k] = mk(1.0f / d[k].x, 1.0f / d[k].y, 1.0f / d[k].z);
-        cur[k] = active[k] ? 0u : kLockstepDone;
+        cur[k] = ray_on(active, k) ? 0u : kLockstepDone;
         tfar_c[k] = walk_bound(tfar[k]);
-        live |= active[k];
-        occ[k] = false;
+        live |= ray_on(active, k);
     }
     const uint32_t n = S.n_nodes;
     // per-lane ray state as integer bit-sets (bit k = ray k) held in VGPRs and updated with selects:
@@ -616,7 +623,8 @@ __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const boo
                 for (int k = 0; k < K; ++k) {
                     if (__ballot((want >> k) & 1u) != 0) {        // wave-uniform
                         float t, u, v;
-                        const bool hit = tri_test_nb(T0, T1, T2, o, d[k], tnear, tfar[k], t, u, v);
+                        const bool hit = tri_test_nb(T0, T1, T2, o, d[k], kOneBound ? tnear_c : tnear,
+                                                     kOneBound ? tfar_c[k] : tfar[k], t, u, v);
                         occb |= (((want >> k) & 1u) && hit) ? (1u << k) : 0u;
                     }
                 }
@@ -638,8 +646,12 @@ __device__ __forceinline__ void occluded_wave_multi(const DevScene& S, const boo
             m = lockstep_step(false, desc, false, m, skip, 0u);
         }
     }
+    if constexpr (std::is_same_v<O, uint32_t>) {
+        occ = occb;
+    } else {
 #pragma unroll
-    for (int k = 0; k < K; ++k) occ[k] = (occb >> k) & 1u;
+        for (int k = 0; k < K; ++k) occ[k] = (occb >> k) & 1u;
+    }
 }
 // one any-hit ray per lane (the K = 1 walk, written out: the leaf loop exits per lane)
 __device__ __forceinline__ bool occluded_wave(const DevScene& S, bool active, vec3 o, vec3 d, float tnear, float tfar) {
@@ -727,12 +739,22 @@ template <int T, int K>
 __device__ __forceinline__ void trace_any_multi(const DevScene& S, const bool* active, vec3 o, const vec3* d,
                                                 float tnear, const float* tfar, bool* occ) {
     if (!trav_lane(T)) {
-        occluded_wave_multi<K>(S, active, o, d, tnear, tfar, occ);
+        occluded_wave_multi<K, false>(S, active, o, d, tnear, tfar, occ);
     } else {   // one walk after the other (measured faster than interleaving the K walks, and than one
                // loop running a lane's walks back to back: that spilled the hot loop, 2.5x slower on C3)
 #pragma unroll
         for (int k = 0; k < K; ++k) occ[k] = occluded_lane<trav_wide(T)>(S, active[k], o, d[k], tnear, tfar[k]);
     }
+}
+// ... the lockstep kinds' walk with the rays' states as bit-sets: bit k of `active` = ray k has a ray, bit k of the
+// result = it is occluded (the one-thread-per-pixel initial pass's three-ray walks)
+template <int T, int K>
+__device__ __forceinline__ uint32_t trace_any_bits(const DevScene& S, uint32_t active, vec3 o, const vec3* d, float tnear,
+                                                   const float* tfar) {
+    static_assert(!trav_lane(T), "the per-lane kinds trace one ray after the other (trace_any_multi)");
+    uint32_t occ = 0u;
+    occluded_wave_multi<K, true>(S, active, o, d, tnear, tfar, occ);
+    return occ;
 }
 template <int T>
 __device__ __forceinline__ bool trace_any(const DevScene& S, bool active, vec3 o, vec3 d, float tnear, float tfar) {
