@@ -1,0 +1,527 @@
+"""Closed-form lighting references for the estimators (tests/test_closed_form_oracle.py on the CPU oracle,
+tests/test_gpu_closed_form.py on the HIP renderer).  TEST INFRASTRUCTURE ONLY.
+
+Everything the estimators are compared with here is float64 numpy written from the rendering equation, not from
+the oracle: Lambert's polygon formula, a stratified quadrature with brute-force visibility, and the furnace value
+(kd + ks) Le.  The module shares no code with oracle/restir_oracle.c and never calls it; the test files hand it a
+`backend` (the oracle or the GPU renderer) that it drives through two methods:
+
+    backend.gbuffer(cf)                          -> (H, W, 19) G-buffer of cf.scene seen from cf.camera
+    backend.mean_image(cf, estimator, seed, n)   -> (H, W, 3) float64 mean of n frames (ReSTIR) / one frame of n spp
+
+Receiver position, normal, kd and ks are read from the G-buffer (pinned bit for bit elsewhere), so the reference is
+evaluated at the very points the renderer shades.
+
+Bounds.  Nothing is compared against the code under test.  The one measured quantity is statistical resolution: for
+each case the oracle ran with MEASURE_SEEDS seeds; SE is the standard deviation of the per-seed ratios divided by
+sqrt(len(SEEDS)), i.e. the standard error of the mean of the SEEDS the tests run (the standard deviation is taken
+over more seeds than the tests run, because one estimated from 4 values is itself only good to ~40 %).  The sum-ratio
+bound is 4 SE and may not exceed SUM_CAP = 2 % (tests/test_oracle.py's estimator-agreement bound).  The per-pixel
+bounds are 1.5 x the oracle's median and 99th percentile of |image - reference| / reference on the seed-averaged
+image.  MEASURED holds those figures.
+"""
+from __future__ import annotations
+
+import functools
+from dataclasses import dataclass, field
+
+import numpy as np
+
+from restir_amd import scenes
+
+W, H = 40, 30
+SEEDS = (123, 7, 99, 2024)                       # the seeds every test runs
+MEASURE_SEEDS = SEEDS + tuple(range(1, 21))     # the 24 seeds the standard deviations were measured over
+SUM_CAP = 0.02                                   # no sum-ratio bound may exceed this (tests/test_oracle.py:506)
+PIXEL_MARGIN = 1.5
+QUIRK_BRACKET = 0.25                             # a reproduced reference quirk stays within +-25 % of its measured deviation
+QUAD_M = 40                                      # QUAD_M^2 = 1600 stratified points per emitter triangle
+# quadrature against the polygon formula on open_scene: the midpoint rule's error is ~ (h / d)^2 / 4 for cell size
+# h = 0.5 / 40 and the nearest receiver-emitter distance d >= 0.5, i.e. ~ 2e-4; asserted at 5e-4 per pixel
+QUAD_VS_POLYGON = 5e-4
+# umbra: the quadrature resolves a visible fraction of 1 / (3 * 1600) of the emitters; a pixel it labels umbra may see
+# at most a few such cells, so its radiance is below 1e-3 of an unoccluded pixel's
+UMBRA_BOUND = 1e-3
+
+LE = (10.0, 6.0, 3.0)
+FURNACE_LE = (2.0, 2.0, 2.0)
+FRAMES = {"open": 192, "blocked": 192, "furnace_steep": 96, "furnace_grazing": 96}
+MIS_SPP = {"open": 256, "blocked": 256, "furnace_steep": 512, "furnace_grazing": 512}
+# cases whose 4 SE at the frame counts above exceeded SUM_CAP: more frames, not a wider bound
+MORE_FRAMES = {("blocked", "debias_contrib_T1"): 2304, ("furnace_steep", "pairwise_T1"): 256,
+               ("furnace_grazing", "pairwise_T1"): 256}
+
+
+def samples_for(scene, estimator):
+    """frames per seed (ReSTIR) or samples per pixel of the one frame per seed (MIS, path)"""
+    if ESTIMATORS[estimator][0] != "restir":
+        return MIS_SPP[scene]
+    return MORE_FRAMES.get((scene, estimator), FRAMES[scene])
+
+
+# ---------------------------------------------------------------- estimators
+def _restir(**kw):
+    base = dict(m_area=4, m_brdf=1, spatial_neighbors=4, spatial_passes=1, do_spatial=0, do_temporal=0,
+                do_visibility_pass=0, reject_dissimilar=0, spatial_mis="constant")
+    base.update(kw)
+    return ("restir", base)
+
+
+MODES = ("constant", "debias_contrib", "debias_z", "balance", "pairwise")
+ESTIMATORS = {"mis": ("mis", {}), "path_nogi": ("path", {}), "initial": _restir(), "temporal": _restir(do_temporal=1)}
+for _m in MODES:
+    for _t in (0, 1):
+        ESTIMATORS[f"{_m}_T{_t}"] = _restir(do_spatial=1, do_temporal=_t, spatial_mis=_m)
+ESTIMATORS["pairwise_T1_vis"] = _restir(do_spatial=1, do_temporal=1, spatial_mis="pairwise", do_visibility_pass=1)
+ESTIMATORS["balance_T1_2pass_reject"] = _restir(do_spatial=1, do_temporal=1, spatial_mis="balance", spatial_passes=2,
+                                                reject_dissimilar=1)
+FURNACE_ESTIMATORS = ("mis", "path_nogi", "initial", "balance_T0", "pairwise_T1")
+
+
+# ---------------------------------------------------------------- scenes
+@dataclass
+class CFScene:
+    name: str
+    scene: scenes.Scene
+    camera: scenes.Camera
+    tris: np.ndarray                  # (T, 3, 3) float64 of the float32 positions the renderer gets
+    shading_normals: np.ndarray       # (T, 3, 3)
+    emissive: np.ndarray              # (T,) bool
+    le: np.ndarray                    # (T, 3)
+    width: int = W
+    height: int = H
+    strips: dict = field(default_factory=dict)     # furnace: name -> scenes.Material
+
+
+def _finish(b, camera, name, width=W, height=H, strips=None):
+    sc = b.build(camera, name)
+    tris = sc.positions.reshape(-1, 3, 3).astype(np.float64)
+    nrm = sc.normals.reshape(-1, 3, 3).astype(np.float64)
+    mf, _ = sc.material_arrays()
+    le = mf[:, 6:9].astype(np.float64)[sc.tri_material]
+    return CFScene(name, sc, camera, tris, nrm, sc.emissive_mask(), le, width, height, strips or {})
+
+
+OPEN_CAMERA = scenes.Camera(eye=(0.0, -3.5, 1.6), at=(0.0, 0.2, 0.2), fov_y=45.0)
+
+
+def _open(blocker):
+    b = scenes._Builder()
+    floor = b.material(scenes.Material(kd=(0.7, 0.6, 0.5), type=scenes.LAMBERT))
+    recv = b.material(scenes.Material(kd=(0.5, 0.6, 0.7), type=scenes.LAMBERT))
+    light = b.material(scenes.Material(le=LE, type=scenes.LAMBERT))
+    b.quad([-3, -3, 0], [3, -3, 0], [3, 1, 0], [-3, 1, 0], floor)
+    b.quad([-1.5, 1, 0], [1.5, 1, 0], [1.5, 1.8, 0.8], [-1.5, 1.8, 0.8], recv)
+    # three coplanar emitter triangles of different areas at z = 1 facing down (clockwise seen from above)
+    b.quad([-0.3, -0.2, 1], [-0.3, 0.3, 1], [0.2, 0.3, 1], [0.2, -0.2, 1], light)
+    b.tris(np.array([[0.5, -0.4, 1, 0.5, 0.1, 1, 0.9, -0.1, 1]]), np.tile([0, 0, -1], (1, 3)), light)
+    if blocker:
+        # two-sided 0.7 x 0.6 quad at z = 0.45 under the emitters: its umbra on the floor is about 0.3 x 0.5
+        blk = b.material(scenes.Material(kd=(0.6, 0.6, 0.6), type=scenes.LAMBERT))
+        b.quad([-0.05, -0.35, 0.45], [0.65, -0.35, 0.45], [0.65, 0.25, 0.45], [-0.05, 0.25, 0.45], blk)
+    return _finish(b, OPEN_CAMERA, "blocked" if blocker else "open")
+
+
+def open_scene():
+    return _open(False)
+
+
+def blocked_scene():
+    return _open(True)
+
+
+FURNACE_CAMERAS = {
+    "steep": (scenes.Camera(eye=(0.0, -0.6, 1.4), at=(0.0, 0.0, 0.0), fov_y=45.0), W, H),
+    # 5 to 11 degrees above the strips' plane; fov 16 at 120 x 24 puts about 150 pixels on every strip
+    "grazing": (scenes.Camera(eye=(0.0, -1.7, 0.22), at=(0.0, 0.1, 0.0), fov_y=16.0), 120, 24),
+}
+STRIPS = {
+    "lambert": scenes.Material(kd=(0.5, 0.4, 0.3), type=scenes.LAMBERT),
+    "phong_n1": scenes.Material(kd=(0.4, 0.35, 0.3), ks=(0.3, 0.3, 0.3), shininess=1.0, type=scenes.PHONG),
+    "phong_n8": scenes.Material(kd=(0.4, 0.35, 0.3), ks=(0.3, 0.3, 0.3), shininess=8.0, type=scenes.PHONG),
+    "spec_n64": scenes.Material(ks=(0.5, 0.6, 0.7), shininess=64.0, type=scenes.PHONG),
+    "phong_n500": scenes.Material(kd=(0.4, 0.35, 0.3), ks=(0.3, 0.3, 0.3), shininess=500.0, type=scenes.PHONG),
+}
+KD_KS_STRIPS = ("phong_n1", "phong_n8", "phong_n500")
+
+
+def _icosphere(subdiv):
+    t = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in
+         [(-1, t, 0), (1, t, 0), (-1, -t, 0), (1, -t, 0), (0, -1, t), (0, 1, t), (0, -1, -t), (0, 1, -t), (t, 0, -1),
+          (t, 0, 1), (-t, 0, -1), (-t, 0, 1)]]
+    f = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6),
+         (7, 1, 8), (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7),
+         (9, 8, 1)]
+    for _ in range(subdiv):
+        mid, nf = {}, []
+
+        def m(a, b):
+            k = (min(a, b), max(a, b))
+            if k not in mid:
+                p = v[a] + v[b]
+                v.append(p / np.linalg.norm(p))
+                mid[k] = len(v) - 1
+            return mid[k]
+
+        for a, b, c in f:
+            ab, bc, ca = m(a, b), m(b, c), m(c, a)
+            nf += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        f = nf
+    return np.asarray(v), np.asarray(f)
+
+
+def furnace_scene(camera="steep"):
+    """Icosphere of radius 2 (320 triangles, flat normals pointing inward, every one emitting FURNACE_LE) around five
+    coplanar strips at z = 0, 0.3 wide in x, side by side."""
+    cam, width, height = FURNACE_CAMERAS[camera]
+    b = scenes._Builder()
+    for i, m in enumerate(STRIPS.values()):
+        x0, x1 = -0.75 + 0.3 * i, -0.45 + 0.3 * i
+        b.quad([x0, -0.6, 0], [x1, -0.6, 0], [x1, 0.8, 0], [x0, 0.8, 0], b.material(m))
+    v, f = _icosphere(2)
+    tri = (2.0 * v[f]).astype(np.float32)                      # (320, 3, 3)
+    t64 = tri.astype(np.float64)
+    n = np.cross(t64[:, 1] - t64[:, 0], t64[:, 2] - t64[:, 0])
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    n *= -np.sign((n * t64.mean(axis=1)).sum(-1))[:, None]      # inward
+    b.tris(tri.reshape(-1, 9), np.repeat(n, 3, axis=0).reshape(-1, 9), b.material(scenes.Material(le=FURNACE_LE)))
+    return _finish(b, cam, f"furnace_{camera}", width, height, dict(STRIPS))
+
+
+@functools.lru_cache(maxsize=None)
+def get_scene(name):
+    return {"open": open_scene, "blocked": blocked_scene, "furnace_steep": lambda: furnace_scene("steep"),
+            "furnace_grazing": lambda: furnace_scene("grazing")}[name]()
+
+
+# ---------------------------------------------------------------- references
+def polygon_irradiance(x, n, poly):
+    """Lambert's formula: the integral of cos(theta) d(omega) over the polygon `poly` (K, 3) seen from the points x
+    (N, 3) with normals n (N, 3), the polygon entirely above each point's horizon: 1/2 |sum_i theta_i Gamma_i . n|,
+    theta_i the angle the i-th edge subtends and Gamma_i the unit normal of the plane through x and that edge."""
+    x, n, poly = np.asarray(x, np.float64), np.asarray(n, np.float64), np.asarray(poly, np.float64)
+    r = poly[None, :, :] - x[:, None, :]
+    r /= np.linalg.norm(r, axis=-1, keepdims=True)
+    r1 = np.roll(r, -1, axis=1)
+    theta = np.arccos(np.clip((r * r1).sum(-1), -1.0, 1.0))
+    g = np.cross(r, r1)
+    g /= np.linalg.norm(g, axis=-1, keepdims=True)
+    return 0.5 * np.abs((theta * (g * n[:, None, :]).sum(-1)).sum(-1))
+
+
+def _strata(m=QUAD_M):
+    """Barycentric coordinates (m*m, 3) of the midpoints of an m x m stratification of the area-uniform square-root map"""
+    u = (np.arange(m) + 0.5) / m
+    r1, r2 = np.meshgrid(u, u, indexing="ij")
+    s = np.sqrt(r1.ravel())
+    return np.stack([1.0 - s, s * (1.0 - r2.ravel()), s * r2.ravel()], -1)
+
+
+def segments_hit(x, y, tris, tmin=1e-6):
+    """Moeller-Trumbore in float64: (N, M) bool, the open segment x[i] -> y[i, j] crosses one of tris (T, 3, 3), both
+    sides counted; t is the fraction of the segment and lies in (tmin, 1 - tmin)."""
+    d = y - x[:, None, :]                                         # (N, M, 3)
+    hit = np.zeros(d.shape[:2], bool)
+    for t in np.asarray(tris, np.float64).reshape(-1, 3, 3):
+        e1, e2 = t[1] - t[0], t[2] - t[0]
+        p = np.cross(d, e2)
+        det = p @ e1
+        ok = np.abs(det) > 1e-300
+        inv = 1.0 / np.where(ok, det, 1.0)
+        s = x - t[0]                                              # (N, 3)
+        u = (p * s[:, None, :]).sum(-1) * inv
+        q = np.cross(s, e1)                                       # (N, 3)
+        v = (d * q[:, None, :]).sum(-1) * inv
+        tt = (q @ e2)[:, None] * inv
+        hit |= ok & (u >= 0) & (v >= 0) & (u + v <= 1) & (tt > tmin) & (tt < 1.0 - tmin)
+    return hit
+
+
+def quadrature_radiance(cf, x, n, kd, visibility=True, chunk=64):
+    """Lambert radiance kd / pi * sum_e Le_e * integral over emitter e of V cos(theta_x) cos(theta_y) / d^2 dA by QUAD_M^2
+    stratified barycentric midpoints per emitter triangle; V from segments_hit against every non-emitter; the cosine at
+    the emitter from its interpolated shading normal.  Returns (radiance (N, 3), visible fraction of the points (N,))."""
+    bary = _strata()
+    et = np.nonzero(cf.emissive)[0]
+    pts = np.concatenate([bary @ cf.tris[t] for t in et])                          # (M, 3)
+    nn = np.concatenate([bary @ cf.shading_normals[t] for t in et])
+    nn /= np.linalg.norm(nn, axis=-1, keepdims=True)
+    area = 0.5 * np.linalg.norm(np.cross(cf.tris[et, 1] - cf.tris[et, 0], cf.tris[et, 2] - cf.tris[et, 0]), axis=-1)
+    wle = np.concatenate([np.tile(cf.le[t] * a / len(bary), (len(bary), 1)) for t, a in zip(et, area)])   # (M, 3)
+    occl = cf.tris[~cf.emissive]
+    out, vis = np.zeros((len(x), 3)), np.ones(len(x))
+    for i in range(0, len(x), chunk):
+        xs, ns = x[i:i + chunk], n[i:i + chunk]
+        d = pts[None] - xs[:, None]
+        r2 = (d * d).sum(-1)
+        d /= np.sqrt(r2)[..., None]
+        g = np.maximum((d * ns[:, None]).sum(-1), 0.0) * np.maximum(-(d * nn[None]).sum(-1), 0.0) / r2
+        if visibility:
+            v = ~segments_hit(xs, np.broadcast_to(pts, (len(xs),) + pts.shape), occl)
+            g = g * v
+            vis[i:i + chunk] = v.mean(-1)
+        out[i:i + chunk] = g @ wle
+    return kd / np.pi * out, vis
+
+
+def polygon_radiance(cf, x, n, kd):
+    e = np.zeros((len(x), 3))
+    for t in np.nonzero(cf.emissive)[0]:
+        e += polygon_irradiance(x, n, cf.tris[t])[:, None] * cf.le[t]
+    return kd / np.pi * e
+
+
+def furnace_expected(kd, ks, le):
+    """Direct radiance of a Phong surface whose specular term is divided by I_M = the integral of (wi . wr)^n cos(theta)
+    over the hemisphere, under uniform incident radiance Le: (kd + ks) Le for every view, exponent and tessellation."""
+    return (np.asarray(kd, np.float64) + np.asarray(ks, np.float64)) * np.asarray(le, np.float64)
+
+
+def validate(cf, x, n):
+    """The scene mistakes that bias a reference silently, counted from the reference's own geometry for the receiver
+    points x with normals n; every count must be zero.
+      * an emitter whose shading normal is not its geometric normal (the renderer takes cos(theta_y) from the shading
+        normal, the closed forms from the plane), or that faces away from a receiver;
+      * an emitter vertex at or below a receiver's horizon (the polygon formula would need clipping);
+      * a receiver-to-emitter segment that crosses another emitter (an occluder the references do not model).
+    The furnace's emitters are the faces of a convex polyhedron around the receivers: the horizon clips nothing that
+    (kd + ks) Le depends on and the faces cannot hide one another, so the last two counts become the receivers that
+    are not strictly inside every face's plane."""
+    et = np.nonzero(cf.emissive)[0]
+    gn = np.cross(cf.tris[:, 1] - cf.tris[:, 0], cf.tris[:, 2] - cf.tris[:, 0])
+    gn /= np.linalg.norm(gn, axis=-1, keepdims=True)
+    sn = cf.shading_normals / np.linalg.norm(cf.shading_normals, axis=-1, keepdims=True)
+    bent = int((np.abs((sn[et] * gn[et, None, :]).sum(-1)).min(axis=1) < 1.0 - 1e-9).sum())
+    facing = ((x[:, None, :] - cf.tris[et, 0][None]) * sn[et, 0][None]).sum(-1)          # (N, E): > 0 in front
+    if cf.name.startswith("furnace"):
+        return {"emitters_with_bent_shading_normal": bent, "receivers_outside_the_enclosure": int((facing <= 0).any(1).sum())}
+    bent += int((facing <= 0).any(axis=0).sum())
+    verts = cf.tris[et].reshape(-1, 3)
+    below = int((((verts[None] - x[:, None]) * n[:, None]).sum(-1) <= 0).sum())
+    bary = _strata(8)
+    blocked = 0
+    for t in et:
+        pts = bary @ cf.tris[t]
+        others = cf.tris[[k for k in et if k != t]]
+        for i in range(0, len(x), 256):
+            xs = x[i:i + 256]
+            blocked += int(segments_hit(xs, np.broadcast_to(pts, (len(xs),) + pts.shape), others).sum())
+    return {"emitters_with_bent_shading_normal": bent, "emitter_vertices_below_a_horizon": below,
+            "segments_crossing_another_emitter": blocked}
+
+
+# ---------------------------------------------------------------- per-scene reference at the G-buffer's points
+@dataclass
+class Reference:
+    mask: np.ndarray            # (H, W) bool: hit, non-emissive (furnace: on a strip)
+    image: np.ndarray           # (H, W) reference radiance summed over the channels (0 outside the mask)
+    regions: dict               # name -> (H, W) bool
+    umbra: np.ndarray | None
+    x: np.ndarray
+    n: np.ndarray
+    quadrature: np.ndarray | None = None   # open scene: the quadrature's image (`image` is the polygon formula's)
+
+
+def reference(cf, g):
+    """The reference image and region masks for the G-buffer g (H, W, 19) of cf."""
+    g = np.asarray(g, np.float64)
+    mask = (g[..., 16] > 0) & (g[..., 12:15].sum(-1) == 0)
+    x, n, kd, ks = g[mask][:, 0:3], g[mask][:, 3:6], g[mask][:, 6:9], g[mask][:, 9:12]
+    img = np.zeros(mask.shape)
+    if cf.name.startswith("furnace"):
+        img[mask] = furnace_expected(kd, np.where(g[mask][:, 17:18] == scenes.PHONG, ks, 0.0), FURNACE_LE).sum(-1)
+        regions = {}
+        for name, m in cf.strips.items():
+            mf = np.array([*m.kd, *m.ks], np.float32).astype(np.float64)
+            regions[name] = mask & (np.abs(g[..., 6:12] - mf).max(-1) == 0) & (g[..., 15] == np.float32(m.shininess))
+        return Reference(mask, img, regions, None, x, n)
+    rad, vis = quadrature_radiance(cf, x, n, kd, visibility=True)
+    img[mask] = rad.sum(-1)
+    if cf.name == "open":
+        pol = np.zeros(mask.shape)
+        pol[mask] = polygon_radiance(cf, x, n, kd).sum(-1)
+        return Reference(mask, pol, {"all": mask.copy()}, None, x, n, quadrature=img)
+    lab = np.full(mask.shape, -1.0)
+    lab[mask] = vis
+    return Reference(mask, img, {"lit": lab == 1.0, "penumbra": (lab > 0.0) & (lab < 1.0)}, lab == 0.0, x, n)
+
+
+# ---------------------------------------------------------------- measuring an estimator against a reference
+def measure(backend, cf, ref, estimator, seeds=SEEDS, frames=None):
+    """Per region: the per-seed sum ratios image / reference, and the median and 99th percentile of the per-pixel
+    |image - reference| / reference of the image averaged over `seeds`; for blocked_scene also the umbra figure (mean
+    umbra radiance over the reference's mean radiance in the lit region).  Images are summed over the channels."""
+    n = samples_for(cf.name, estimator) if frames is None else frames
+    imgs = [backend.mean_image(cf, estimator, s, n).astype(np.float64).sum(-1) for s in seeds]
+    assert all(np.isfinite(i).all() for i in imgs)
+    mean = np.mean(imgs, axis=0)
+    out = {}
+    for name, m in ref.regions.items():
+        rel = np.abs(mean[m] - ref.image[m]) / ref.image[m]
+        out[name] = {"ratios": [float(i[m].sum() / ref.image[m].sum()) for i in imgs],
+                     "median": float(np.median(rel)), "p99": float(np.percentile(rel, 99)), "pixels": int(m.sum())}
+    if ref.umbra is not None:
+        out["umbra"] = {"level": float(mean[ref.umbra].mean() / ref.image[ref.regions["lit"]].mean()),
+                        "pixels": int(ref.umbra.sum())}
+    return out
+
+
+# ---------------------------------------------------------------- the recorded oracle figures and the bounds from them
+# "scene/estimator/region": (ratio: mean over SEEDS, sd: over MEASURE_SEEDS, per-pixel median, p99) -- the oracle's figures
+MEASURED = {
+    "open/mis/all": (0.9996, 0.00151, 0.0084, 0.0429),
+    "open/initial/all": (0.9996, 0.00090, 0.0047, 0.0224),
+    "open/constant_T0/all": (0.9994, 0.00079, 0.0026, 0.0123),
+    "open/debias_contrib_T0/all": (0.9999, 0.00193, 0.0089, 0.0441),
+    "open/debias_z_T0/all": (0.9994, 0.00079, 0.0026, 0.0123),
+    "open/balance_T0/all": (0.9996, 0.00095, 0.0026, 0.0120),
+    "open/pairwise_T0/all": (0.9995, 0.00080, 0.0027, 0.0119),
+    "open/pairwise_T1_vis/all": (0.9996, 0.00152, 0.0020, 0.0093),
+    "blocked/mis/lit": (0.9993, 0.00258, 0.0085, 0.0375),
+    "blocked/mis/penumbra": (0.9972, 0.00531, 0.0210, 0.3314),
+    "blocked/initial/lit": (0.9993, 0.00120, 0.0047, 0.0226),
+    "blocked/initial/penumbra": (0.9994, 0.00322, 0.0110, 0.1859),
+    "blocked/constant_T0/lit": (0.9491, 0.00139, 0.0039, 0.1744),
+    "blocked/constant_T0/penumbra": (0.8822, 0.00285, 0.1204, 0.3446),
+    "blocked/debias_contrib_T0/lit": (1.0010, 0.00383, 0.0096, 0.0546),
+    "blocked/debias_contrib_T0/penumbra": (1.0004, 0.00453, 0.0140, 0.1213),
+    "blocked/debias_z_T0/lit": (0.9997, 0.00163, 0.0029, 0.0136),
+    "blocked/debias_z_T0/penumbra": (0.9992, 0.00318, 0.0077, 0.1442),
+    "blocked/balance_T0/lit": (1.0001, 0.00128, 0.0031, 0.0158),
+    "blocked/balance_T0/penumbra": (0.9993, 0.00326, 0.0062, 0.1096),
+    "blocked/pairwise_T0/lit": (0.9994, 0.00118, 0.0028, 0.0128),
+    "blocked/pairwise_T0/penumbra": (0.9992, 0.00295, 0.0074, 0.1420),
+    "blocked/pairwise_T1_vis/lit": (0.9997, 0.00284, 0.0020, 0.0156),
+    "blocked/pairwise_T1_vis/penumbra": (0.9975, 0.00385, 0.0094, 0.2596),
+    "furnace_steep/mis/lambert": (1.0009, 0.00076, 0.0040, 0.0153),
+    "furnace_steep/mis/phong_n1": (0.5926, 0.00072, 0.4082, 0.4265),
+    "furnace_steep/mis/phong_n8": (0.7070, 0.00093, 0.2955, 0.3177),
+    "furnace_steep/mis/spec_n64": (1.0005, 0.00038, 0.0014, 0.0066),
+    "furnace_steep/mis/phong_n500": (0.9791, 0.00124, 0.0208, 0.0383),
+    "furnace_steep/initial/lambert": (0.9997, 0.00200, 0.0147, 0.0535),
+    "furnace_steep/initial/phong_n1": (1.0016, 0.00268, 0.0161, 0.0559),
+    "furnace_steep/initial/phong_n8": (1.0001, 0.00360, 0.0154, 0.0564),
+    "furnace_steep/initial/spec_n64": (1.0005, 0.00194, 0.0109, 0.0371),
+    "furnace_steep/initial/phong_n500": (0.9977, 0.00395, 0.0160, 0.0569),
+    "furnace_steep/pairwise_T1/lambert": (1.0011, 0.00263, 0.0021, 0.0090),
+    "furnace_steep/pairwise_T1/phong_n1": (1.0023, 0.00258, 0.0032, 0.0124),
+    "furnace_steep/pairwise_T1/phong_n8": (1.0023, 0.00367, 0.0053, 0.0248),
+    "furnace_steep/pairwise_T1/spec_n64": (0.9967, 0.00639, 0.0131, 0.0534),
+    "furnace_steep/pairwise_T1/phong_n500": (0.9977, 0.00861, 0.0248, 0.0813),
+    "furnace_grazing/path_nogi/lambert": (1.0011, 0.00079, 0.0042, 0.0128),
+    "furnace_grazing/path_nogi/phong_n1": (0.7001, 0.00146, 0.3002, 0.3302),
+    "furnace_grazing/path_nogi/phong_n8": (0.8435, 0.00234, 0.1571, 0.1861),
+    "furnace_grazing/path_nogi/spec_n64": (1.0038, 0.00291, 0.0113, 0.0362),
+    "furnace_grazing/path_nogi/phong_n500": (0.9969, 0.00113, 0.0070, 0.0226),
+    "furnace_grazing/balance_T0/lambert": (1.0001, 0.00338, 0.0068, 0.0337),
+    "furnace_grazing/balance_T0/phong_n1": (0.9997, 0.00458, 0.0093, 0.0403),
+    "furnace_grazing/balance_T0/phong_n8": (1.0018, 0.00462, 0.0112, 0.0484),
+    "furnace_grazing/balance_T0/spec_n64": (1.0076, 0.00644, 0.0153, 0.0607),
+    "furnace_grazing/balance_T0/phong_n500": (1.0033, 0.00510, 0.0143, 0.0461),
+    "open/path_nogi/all": (0.9996, 0.00151, 0.0084, 0.0429),
+    "open/temporal/all": (0.9996, 0.00088, 0.0047, 0.0221),
+    "open/constant_T1/all": (0.9988, 0.00233, 0.0021, 0.0090),
+    "open/debias_contrib_T1/all": (1.0038, 0.00777, 0.0121, 0.0557),
+    "open/debias_z_T1/all": (0.9988, 0.00233, 0.0021, 0.0090),
+    "open/balance_T1/all": (0.9985, 0.00211, 0.0020, 0.0087),
+    "open/pairwise_T1/all": (0.9996, 0.00152, 0.0020, 0.0093),
+    "open/balance_T1_2pass_reject/all": (1.0013, 0.00269, 0.0016, 0.0099),
+    "blocked/path_nogi/lit": (0.9993, 0.00258, 0.0085, 0.0375),
+    "blocked/path_nogi/penumbra": (0.9972, 0.00531, 0.0210, 0.3314),
+    "blocked/temporal/lit": (0.9992, 0.00121, 0.0048, 0.0223),
+    "blocked/temporal/penumbra": (0.9994, 0.00316, 0.0109, 0.1909),
+    "blocked/constant_T1/lit": (0.8402, 0.00241, 0.0464, 0.3779),
+    "blocked/constant_T1/penumbra": (0.7384, 0.00399, 0.2789, 0.5357),
+    "blocked/debias_contrib_T1/lit": (1.0007, 0.00696, 0.0037, 0.0254),
+    "blocked/debias_contrib_T1/penumbra": (0.9997, 0.00537, 0.0062, 0.0840),
+    "blocked/debias_z_T1/lit": (1.0001, 0.00400, 0.0024, 0.0189),
+    "blocked/debias_z_T1/penumbra": (1.0032, 0.00550, 0.0095, 0.2193),
+    "blocked/balance_T1/lit": (1.0017, 0.00496, 0.0022, 0.0219),
+    "blocked/balance_T1/penumbra": (1.0020, 0.00712, 0.0095, 0.2601),
+    "blocked/pairwise_T1/lit": (1.0001, 0.00264, 0.0021, 0.0157),
+    "blocked/pairwise_T1/penumbra": (0.9992, 0.00370, 0.0069, 0.2041),
+    "blocked/balance_T1_2pass_reject/lit": (1.0010, 0.00521, 0.0018, 0.0168),
+    "blocked/balance_T1_2pass_reject/penumbra": (1.0000, 0.00804, 0.0094, 0.1945),
+    "furnace_steep/path_nogi/lambert": (1.0009, 0.00076, 0.0040, 0.0153),
+    "furnace_steep/path_nogi/phong_n1": (0.5926, 0.00072, 0.4082, 0.4265),
+    "furnace_steep/path_nogi/phong_n8": (0.7070, 0.00093, 0.2955, 0.3177),
+    "furnace_steep/path_nogi/spec_n64": (1.0005, 0.00038, 0.0014, 0.0066),
+    "furnace_steep/path_nogi/phong_n500": (0.9791, 0.00124, 0.0208, 0.0383),
+    "furnace_steep/balance_T0/lambert": (0.9994, 0.00241, 0.0074, 0.0275),
+    "furnace_steep/balance_T0/phong_n1": (1.0012, 0.00236, 0.0071, 0.0336),
+    "furnace_steep/balance_T0/phong_n8": (0.9998, 0.00395, 0.0088, 0.0304),
+    "furnace_steep/balance_T0/spec_n64": (1.0010, 0.00327, 0.0122, 0.0559),
+    "furnace_steep/balance_T0/phong_n500": (0.9977, 0.00421, 0.0156, 0.0538),
+    "furnace_grazing/mis/lambert": (1.0011, 0.00079, 0.0042, 0.0128),
+    "furnace_grazing/mis/phong_n1": (0.7001, 0.00146, 0.3002, 0.3302),
+    "furnace_grazing/mis/phong_n8": (0.8435, 0.00234, 0.1571, 0.1861),
+    "furnace_grazing/mis/spec_n64": (1.0038, 0.00291, 0.0113, 0.0362),
+    "furnace_grazing/mis/phong_n500": (0.9969, 0.00113, 0.0070, 0.0226),
+    "furnace_grazing/initial/lambert": (1.0005, 0.00313, 0.0124, 0.0455),
+    "furnace_grazing/initial/phong_n1": (0.9996, 0.00425, 0.0164, 0.0678),
+    "furnace_grazing/initial/phong_n8": (0.9992, 0.00396, 0.0226, 0.0651),
+    "furnace_grazing/initial/spec_n64": (1.0056, 0.00486, 0.0266, 0.0942),
+    "furnace_grazing/initial/phong_n500": (1.0046, 0.00472, 0.0190, 0.0568),
+    "furnace_grazing/pairwise_T1/lambert": (1.0013, 0.00327, 0.0035, 0.0146),
+    "furnace_grazing/pairwise_T1/phong_n1": (0.9992, 0.00359, 0.0036, 0.0146),
+    "furnace_grazing/pairwise_T1/phong_n8": (0.9997, 0.00444, 0.0046, 0.0214),
+    "furnace_grazing/pairwise_T1/spec_n64": (1.0021, 0.00620, 0.0101, 0.0344),
+    "furnace_grazing/pairwise_T1/phong_n500": (1.0025, 0.00508, 0.0128, 0.0500),
+}
+
+# Reference behaviour that is not the closed form ("Quirks reproduced"): asserted darker than the
+# reference by more than 4 SE and within QUIRK_BRACKET of the recorded deviation.
+#  * CONSTANT spatial weights with an occluder: M counts neighbours whose domain does not contain the sample --
+#    pg/ReSTIRIntegrator.cpp:388 "float rcpM = M > 0 ? 1.0f / static_cast<float> (M) : 0.0f;", :406 "misWeight{ rcpM }",
+#    and the CONSTANT branch at :483 applies no correction.
+#  * MIS / path on a material with kd and ks: evaluateLightingGI returns the sampled lobe's f_r over the mixture pdf --
+#    pg/MaterialPhong.cpp:41 "f_r = diffuse * glm::one_over_pi<float>();" or :54 "f_r = specular * i_m * glm::pow(...)",
+#    then :60 "float pdf = pdfDiffuse + pdfSpecular;".
+# A third deviation is resolved by 24 seeds but lies inside every 4 SE bound of the 4-seed tests, so it is recorded in
+# DESIGN.md and not asserted: BRDF rays start at hitPoint + normalOffset * normal (pg/DirectMISIntegrator.cpp:106,
+# pg/ReSTIRIntegrator.cpp:139) while the cosines are taken from hitPoint, +0.05 % (steep) to +0.3 % (grazing, n = 64).
+QUIRKS = {("blocked", "constant_T0"), ("blocked", "constant_T1")} | {
+    (sc, est, strip) for sc in ("furnace_steep", "furnace_grazing") for est in ("mis", "path_nogi") for strip in KD_KS_STRIPS}
+
+
+def is_quirk(scene, estimator, region):
+    return (scene, estimator) in QUIRKS or (scene, estimator, region) in QUIRKS
+
+
+def bounds(scene, estimator, region):
+    """(SE of the mean over SEEDS, sum-ratio bound 4 SE, per-pixel median bound, per-pixel p99 bound)"""
+    _, sd, median, p99 = MEASURED[f"{scene}/{estimator}/{region}"]
+    se = sd / np.sqrt(len(SEEDS))
+    return se, 4.0 * se, PIXEL_MARGIN * median, PIXEL_MARGIN * p99
+
+
+def check(scene, estimator, result, say=print):
+    """Assert one measure() result against the bounds.  Returns nothing; prints every figure before it asserts."""
+    failures = []
+    for region, r in result.items():
+        if region == "umbra":
+            say(f"[closed-form] {scene}/{estimator}/umbra: level {r['level']:.3g} over {r['pixels']} pixels")
+            if not r["level"] <= UMBRA_BOUND:
+                failures.append(f"umbra level {r['level']:.3g} > {UMBRA_BOUND}")
+            continue
+        se, sum_bound, med_bound, p99_bound = bounds(scene, estimator, region)
+        ratio = float(np.mean(r["ratios"]))
+        say(f"[closed-form] {scene}/{estimator}/{region}: ratio {ratio:.4f} (SE {se:.4f}, bound {sum_bound:.4f}) "
+            f"per-pixel median {r['median']:.4f} (<= {med_bound:.4f}) p99 {r['p99']:.4f} (<= {p99_bound:.4f}) "
+            f"over {r['pixels']} pixels")
+        assert sum_bound <= SUM_CAP, (scene, estimator, region, sum_bound)
+        if is_quirk(scene, estimator, region):
+            dev = MEASURED[f"{scene}/{estimator}/{region}"][0] - 1.0
+            if not ratio < 1.0 - 4.0 * se:
+                failures.append(f"{region}: quirk gone, ratio {ratio:.4f} not below 1 - 4 SE = {1 - 4 * se:.4f}")
+            if not abs((ratio - 1.0) - dev) <= QUIRK_BRACKET * abs(dev):
+                failures.append(f"{region}: quirk changed, deviation {ratio - 1:.4f} recorded {dev:.4f}")
+            continue
+        if not abs(ratio - 1.0) <= sum_bound:
+            failures.append(f"{region}: sum ratio {ratio:.4f} off by more than {sum_bound:.4f}")
+        if not r["median"] <= med_bound:
+            failures.append(f"{region}: per-pixel median {r['median']:.4f} > {med_bound:.4f}")
+        if not r["p99"] <= p99_bound:
+            failures.append(f"{region}: per-pixel p99 {r['p99']:.4f} > {p99_bound:.4f}")
+    assert not failures, f"{scene}/{estimator}: " + "; ".join(failures)
