@@ -12,6 +12,7 @@
 #include "../../include/restir_c.h"
 #include "rs_image.h"
 #include "rs_internal.h"
+#include "rs_frame_ring.h"
 
 #include <cmath>
 #include <cstdio>
@@ -38,13 +39,28 @@ using namespace rs;
 
 static thread_local std::string g_last_error;
 
+// One copy of everything a geometry update rewrites: the binary BVH, its leaf triangles, the light tables and the
+// 8-wide tree of the per-lane walks (rs_scene.h; built on the GPU with the binary tree, rs_wide_build.hip, and refit
+// with it when the positions move, rs_refit.h).
+struct GeoCopy {
+    float4 *nodes = nullptr, *tris = nullptr, *emis = nullptr;
+    float* cdf = nullptr;
+    int* cdf_guide = nullptr;
+    WideBvh wide;
+};
+struct GeoBytes { size_t nodes, tris, emis, cdf, guide; };
+
 struct rs_scene {
     rs_context* ctx = nullptr;
     uint32_t n_tris = 0, n_emis = 0, n_mats = 0, n_nodes = 0;
     float* d_pos = nullptr;
-    float4 *d_nodes = nullptr, *d_tris = nullptr, *d_tri_nrm = nullptr, *d_mats = nullptr, *d_emis = nullptr;
-    float* d_cdf = nullptr;
-    int* d_cdf_guide = nullptr;
+    float4 *d_tri_nrm = nullptr, *d_mats = nullptr;
+    // pipelined updates (frames in flight): the refit and the light tables go to the alternate copy, on the next
+    // frame's lane stream, while earlier frames still read the current copy; the copies then swap.  gen counts swaps
+    // (a frame remembers the one it read).  alt also holds the previous geometry generation (a_geo below).
+    GeoCopy geo, alt;
+    int gen = 0;
+    bool wide_on = false;
     float build_ms = 0.0f;
     float box_eps = 0.0f;                 // closest-hit box margin (rs_wide.h box_epsilon), set at the last full build
     // host copies (rs_scene_rebuild re-derives the tables on the host)
@@ -57,23 +73,11 @@ struct rs_scene {
     float ecen[3] = {0.0f, 0.0f, 0.0f};    // centre of the emitter centroids' bounds (the sorted spatial pass's key)
     int *d_refit_order = nullptr, *d_refit_lvl = nullptr;
     std::vector<int> refit_lvl;
-    // 8-wide tree of the per-lane walks (rs_scene.h), built on the GPU with the binary tree (rs_wide_build.hip)
-    // and refit with it when the positions move (rs_refit.h); a_wide = its second copy for pipelined updates
-    // and the previous geometry generation (like a_nodes below)
-    WideBvh wide, a_wide;
-    bool wide_on = false;
     float* h_stage[2] = {nullptr, nullptr};
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     int stage_i = 0;
-    // pipelined updates (frames in flight): the refit and the light tables go to a second copy of the
-    // BVH / triangles / light tables, on the next frame's lane stream, while earlier frames still read the
-    // current copy; the copies then swap.  gen counts swaps (a frame remembers the one it read).
-    float4 *a_nodes = nullptr, *a_tris = nullptr, *a_emis = nullptr;
-    float* a_cdf = nullptr;
-    int* a_cdf_guide = nullptr;
-    int gen = 0;
     // geometry generation (every rs_scene_update_positions; not a rebuild: same positions) and the
-    // generation the a_* copy (+ a_tri_nrm when those normals differ) holds as the previous geometry --
+    // generation the alt copy (+ a_tri_nrm when those normals differ) holds as the previous geometry --
     // a tile's temporal pass rebuilds a previous-frame G element against the previous frame's geometry
     uint32_t geo_gen = 0, a_geo = 0xffffffffu;
     float4* a_tri_nrm = nullptr;
@@ -92,168 +96,157 @@ struct rs_scene {
     mutable int trav_choice = -1;
     mutable int trav_runs[2] = {0, 0};
     mutable float trav_ms[2] = {0.0f, 0.0f};
+    GeoBytes geo_bytes() const {
+        return {2 * ((size_t)n_nodes + 1) * sizeof(float4), 3 * (size_t)n_tris * sizeof(float4),
+                8 * (size_t)n_emis * sizeof(float4), (size_t)std::max(1u, n_emis) * sizeof(float), (kCdfGuide + 1) * sizeof(int)};
+    }
     DevScene dev() const {
         DevScene S;
-        S.nodes = d_nodes; S.tris = d_tris; S.tri_nrm = d_tri_nrm; S.mats = d_mats; S.emis = d_emis; S.cdf = d_cdf; S.cdf_guide = d_cdf_guide;
+        S.nodes = geo.nodes; S.tris = geo.tris; S.tri_nrm = d_tri_nrm; S.mats = d_mats; S.emis = geo.emis; S.cdf = geo.cdf; S.cdf_guide = geo.cdf_guide;
         S.n_nodes = n_nodes; S.n_tris = n_tris; S.n_emis = n_emis; S.n_mats = n_mats;
         S.tri_uv = d_uv; S.tri_tan = d_tan; S.tex = d_tex; S.texd = d_texd; S.sky = sky;
-        S.wnodes = wide_on ? wide.nodes : nullptr; S.wtris = wide.tris; S.n_wnodes = wide_on ? wide.n_nodes : 0u;
+        S.wnodes = wide_on ? geo.wide.nodes : nullptr; S.wtris = geo.wide.tris; S.n_wnodes = wide_on ? geo.wide.n_nodes : 0u;
         S.ebucket = d_ebucket;
         S.ecen = vec3{ecen[0], ecen[1], ecen[2]};
         S.box_eps = box_eps;
         return S;
     }
-    // the geometry of generation `g` if this scene still holds it (current, or the a_* copy of g == a_geo)
+    // the geometry of generation `g` if this scene still holds it (current, or the alt copy of g == a_geo)
     bool dev_of(uint32_t g, DevScene& S) const {
         S = dev();
         if (g == geo_gen) return true;
-        if (g != a_geo || !a_nodes) return false;
-        S.nodes = a_nodes; S.tris = a_tris;
+        if (g != a_geo || !alt.nodes) return false;
+        S.nodes = alt.nodes; S.tris = alt.tris;
         if (a_nrm) S.tri_nrm = a_tri_nrm;
-        const bool w = wide_on && a_wide.nodes;    // the refit trees of that generation
-        S.wnodes = w ? a_wide.nodes : nullptr; S.wtris = w ? a_wide.tris : nullptr; S.n_wnodes = w ? a_wide.n_nodes : 0u;
+        const bool w = wide_on && alt.wide.nodes;    // the refit trees of that generation
+        S.wnodes = w ? alt.wide.nodes : nullptr; S.wtris = w ? alt.wide.tris : nullptr; S.n_wnodes = w ? alt.wide.n_nodes : 0u;
         return true;
     }
 };
 
 enum { EV_BEGIN, EV_INIT, EV_VIS, EV_TEMPORAL, EV_SPATIAL, EV_SHADE, EV_DONE, EV_COUNT };
 
-// Frame pipelining ("run-ahead", depth D <= kMaxAhead): frames rotate over D+1 internal "lane"
-// streams, frame f running entirely on lane f mod (D+1), so up to D+1 consecutive frames are in flight
-// at once: one frame's G-buffer + initial pass (which reads nothing of earlier frames) overlaps the
-// previous frames' later passes, halo exchanges and gathers, and the tails of their kernels.  Only the
-// temporal pass depends on the previous frame (its final reservoirs and G-buffer): it waits for that
-// frame's completion event.  Each lane owns its framebuffer, ray-count slots and counters; the G ring
-// holds D+2 buffers (frames f-D-1..f), the reservoir ring 3D+2 (the buffers frames f-D..f-1 touch stay
-// apart from the two frame f writes).  The context's stream waits for every frame's completion, so
-// its semantics are those of a sequential renderer.  D = 0 runs everything on the context's stream.
-// Work enqueued on the context's stream between frames (geometry updates, MIS frames, sky changes)
-// makes the next frame's lane wait for it.
-constexpr int kMaxAhead = RS_MAX_AHEAD, kLanes = kMaxAhead + 1, kGRing = kMaxAhead + 2, kRRing = 3 * kMaxAhead + 2;
+// Run-ahead lanes and the rings of frames in flight: rs_frame_ring.h (the ordering rules, kMaxAhead, kLanes, kGRing,
+// kRRing).  Everything a lane owns:
+struct Lane {
+    hipStream_t stream = nullptr;          // frame stream (run-ahead); frame f on lane f mod (D+1)
+    float* fb = nullptr;                   // framebuffer (lane 0's allocated at create, others on demand)
+    Counters* cnt = nullptr;               // the frame's ray counts; red = k_reduce_counts partials + ticket
+    ulonglong2* red = nullptr;
+    uint2* part = nullptr;                 // per-wave ray-count slots of the lane's frame (use_parts, count_slot)
+    size_t part_cap = 0, part_used = 0;
+    uint32_t* qctr = nullptr;              // persistent-wave tile queue (rs_passes.h TileQ): 4 words
+    float* candw = nullptr;                // the sorted initial pass's candidate weights (FrameConst::cand_w)
+    float4* candr = nullptr;               // ... and its shadow rays (FrameConst::cand_ray)
+    size_t cand_slots = 0;                 // wave slots candw / candr hold (ensure_handoff)
+    hipEvent_t wait = nullptr;             // the lane's last frame ran on the context's stream: its done event
+    const rs_scene* scene = nullptr;       // the scene copy (scene, gen) the lane's last frame read and that frame's
+    int gen = 0;                           // done event (pipelined scene updates)
+    hipEvent_t done = nullptr;
+    bool prevgeo = false;                  // the lane's last frame rebuilt G elements from the alt geometry copy
+    hipEvent_t fb_read = nullptr;          // the readback its framebuffer is under (its next frame waits for it)
+};
+
+// The frame / tile in flight (and, between frames, the last one).  rs_tile_begin starts from a fresh value.
+struct Frame {
+    bool active = false;
+    const rs_scene* scene = nullptr;
+    FrameConst F = {};
+    rs_frame_params P = {};
+    rs_tile_desc tile = {};
+    int ra = 0, rb = 1, rcur = 0, last = 2;  // reservoir ring: this frame's two buffers, the current one, the previous frame's final
+    bool temporal_ran = false, spatial_ran = false, shade_fused = false, ev_temporal = false;
+    hipStream_t fs = nullptr;              // its stream (a lane's, or the context's when D = 0 or it must follow that stream)
+    int li = 0, slot = 0;                  // its lane index; its slot of the event ring
+    hipEvent_t* ev = nullptr;              // = evr[slot]
+    hipEvent_t prev_done = nullptr;        // completion event of the frame before it (temporal waits)
+    int trav = TRAV_LOCKSTEP;              // traversal kind (rs_scene.h Trav)
+    bool twide = false;                    // its scene has the 8-wide tree live (kernel template bit)
+    bool tuning = false, tune_rows = false;   // a traversal-tuning frame; it also records per-row cost
+    int tune_n = 0;                        // tune_ev recorded so far
+    bool split = false;                    // candidate-split initial pass (rs_passes.h k_gbuffer_initial_split)
+    // the copy generation of `scene` it reads; the geometry generation of the frame before it (a tile's temporal
+    // rebuild of a previous-frame G element traces the previous frame's geometry, rs_scene::dev_of)
+    int frame_gen = 0;
+    const rs_scene* geo_prev_scene = nullptr;
+    uint32_t geo_prev = 0;
+    bool prevgeo_read = false;
+};
+
+// Modes from the environment (read_switches, at rs_context_create); trav_mode and split_mode also have setters.
+struct Switches {
+    int trav_mode = RS_TRAVERSAL_AUTO;     // RESTIR_TRAVERSAL=lockstep|lane
+    int split_mode = RS_SPLIT_AUTO;        // RESTIR_SPLIT: candidate-split initial pass
+    int persist_sorted = RS_SPLIT_AUTO;    // RESTIR_PERSIST_SORTED: the sorted pass by persistent waves
+    int sort_mode = RS_SPLIT_AUTO;         // RESTIR_SORT: wave-sorted initial pass (AUTO: per-lane walks)
+    int sort_spatial = RS_SPLIT_AUTO;      // RESTIR_SORT_SPATIAL: wave-sorted, CONSTANT MIS, k <= 8 (AUTO: per-lane walks -- C3 2.21 -> 1.87 ms; lockstep C5 0.228 -> 0.250)
+    int sort_temporal = RS_SPLIT_AUTO;     // RESTIR_SORT_TEMPORAL=off: per-ray walks instead of wave-sorted temporal rays
+    bool sep_margin = true;                // RESTIR_MARGIN_SPLIT=off: a band's G-buffer margin rows not in their own launch
+    bool light_lds = true;                 // RESTIR_LIGHT_LDS=off: global light tables (use_light_lds)
+    bool order_on = true;                  // RESTIR_TILE_ORDER=off: row-major dispatch
+    bool readback_kernel = false;          // RESTIR_READBACK=kernel: a copy kernel instead of the DMA engine
+};
+
 struct rs_context {
     int device = 0, W = 0, H = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    hipStream_t lane[kLanes] = {};         // frame streams (run-ahead); frame f on lane f mod (D+1)
-    int ahead = kMaxAhead;                 // run-ahead depth D (rs_context_set_run_ahead)
-    hipStream_t fs = nullptr;              // stream of the frame in flight (a lane, or `stream` when D = 0)
-    int li = 0;                            // its lane index (0 when D = 0)
+    int cus = 256, wave_slots = 0;         // CUs; resident wave capacity of the device at the initial pass's budget
+    Switches sw;
+    Lane lanes[kLanes];
+    Frame fr;
+    int ahead = kMaxAhead, fb_ring = 1;    // run-ahead depth D (rs_context_set_run_ahead, RESTIR_RUNAHEAD); frame ring
+    // history: what persists from frame to frame
     bool join_next = true;                 // the next frame waits for the context's stream
     GBuf G[kGRing] = {};
     GCam gcam[kGRing] = {};
     float ginv[kGRing][9] = {};            // each slot's mat3(invViewMat) (a tile's temporal pass rebuilds G)
-    int gcur = 0, gprev = 0;
+    int gcur = 0, gprev = 0;               // G-buffer ring cursor: G[gcur] the last frame begun, G[gprev] the one before
     float4* R[kRRing] = {};
-    int r_last = 2;
+    int r_last = 2;                        // the last finished frame's final reservoirs
     int rhist[kMaxAhead][3];               // {ra, rb, last} of the previous frames (most recent first)
-    float* fb = nullptr;                   // the framebuffer of the frame in flight / last frame
-    float* fbs[kLanes] = {};               // per-lane framebuffers (fbs[0] allocated at create, others on demand)
-    int fb_ring = 1;
+    uint64_t seq = 0, frames = 0;          // frames begun; frames finished since rs_reset_history
+    hipEvent_t last_done = nullptr;        // completion event of the last finished frame
+    hipEvent_t prev_begin = nullptr;       // start event of the last frame begun
+    const rs_scene* geo_last_scene = nullptr;   // geometry generation of the last finished frame
+    uint32_t geo_last = 0;
+    uint64_t prevgeo_missing = 0;          // rebuilds that had to use the current geometry (two updates between frames)
+    rs_camera cam_last = {};               // camera of the last frame (rs_export_png's sidecar)
     float* d_rowcost = nullptr;            // per-row wave time while tracking (rs_context_track_row_costs)
     bool track_rows = false;
-    Counters* d_cnt = nullptr;             // = cnts[li]
-    Counters* cnts[kLanes] = {};
-    Counters* h_cnt = nullptr;
-    uint2* d_part = nullptr;               // per-wave ray-count slots of this frame's launches (= parts[pk])
-    size_t part_cap = 0, part_used = 0;
-    uint2* parts[kLanes] = {};             // per-lane slot buffers
-    size_t part_caps[kLanes] = {};
-    int pk = 0;
-    Counters* d_tot = nullptr;             // running totals over frames (rs_get_timing_totals)
-    ulonglong2* d_red = nullptr;           // k_reduce_counts partials + ticket (= reds[li])
-    ulonglong2* reds[kLanes] = {};
-    uint32_t* qctr[kLanes] = {};           // persistent-wave tile queues (rs_passes.h TileQ): 4 words per lane
-    float* candw[kLanes] = {};             // the sorted initial pass's candidate weights (FrameConst::cand_w), per lane
-    float4* candr[kLanes] = {};            // ... and its shadow rays (FrameConst::cand_ray), per lane
-    size_t cand_slots[kLanes] = {};        // wave slots candw / candr hold (ensure_handoff)
-    int persist_sorted = RS_SPLIT_AUTO;    // RESTIR_PERSIST_SORTED: the sorted pass by persistent waves
+    Counters *h_cnt = nullptr, *d_tot = nullptr;   // readback staging; running totals over frames (rs_get_timing_totals)
     int persist_sorted_wgs[4] = {};
     // pass timing without a per-frame host sync: every frame records into its own slot of an event
     // ring; slots are folded into the running totals lazily (when reused, or on rs_get_timing_totals)
     static constexpr int kEvRing = 64;
     hipEvent_t evr[kEvRing][EV_COUNT] = {};
     bool ev_pending[kEvRing] = {};
-    int slot = 0;
-    uint64_t seq = 0;
     double tot_ms[6] = {};                 // gbuffer_initial, visibility, temporal, spatial, shade, total
     uint64_t tot_frames = 0;
-    hipEvent_t ev[EV_COUNT] = {};          // the frame in flight's slot
-    hipEvent_t ev_gt[2] = {};              // rs_render_direct_mis launch
-    uint64_t frames = 0;
+    hipEvent_t ev_gt[2] = {};              // ground-truth render launch
     std::string err;
-    // frame / tile in flight
-    bool active = false;
-    const rs_scene* scene = nullptr;
-    FrameConst F = {};
-    rs_frame_params P = {};
-    rs_tile_desc tile = {};
-    int ra = 0, rb = 1, rcur = 0, last = 2;
-    bool temporal_ran = false, spatial_ran = false, shade_fused = false, ev_temporal = false;
-    // traversal kind (rs_scene.h Trav): requested mode, kind of the frame in flight, tuning frame flag
-    int trav_mode = RS_TRAVERSAL_AUTO;
-    hipEvent_t last_done = nullptr;        // completion event of the last finished frame
-    hipEvent_t prev_done = nullptr;        // ... of the frame before the one in flight (temporal waits)
-    hipEvent_t prev_begin = nullptr;       // start event of the last frame begun
-    hipEvent_t lane_wait[kLanes] = {};     // a lane's last frame ran on the context's stream: its done event
-    // per lane: the scene copy its last frame read and that frame's done event (pipelined scene updates)
-    const rs_scene* lane_scene[kLanes] = {};
-    int lane_gen[kLanes] = {};
-    hipEvent_t lane_done[kLanes] = {};
-    bool lane_prevgeo[kLanes] = {};        // the lane's last frame rebuilt G elements from the a_* geometry copy
-    // geometry generation of the last finished frame / the frame in progress (a tile's temporal rebuild of
-    // a previous-frame G element traces the previous frame's geometry, rs_scene::dev_of)
-    const rs_scene* geo_last_scene = nullptr;
-    uint32_t geo_last = 0, geo_prev = 0;
-    const rs_scene* geo_prev_scene = nullptr;
-    bool prevgeo_read = false;
-    uint64_t prevgeo_missing = 0;          // rebuilds that had to use the current geometry (two updates between frames)
-    const rs_scene* frame_scene = nullptr;   // the frame in progress: scene and copy generation
-    int frame_gen = 0;
-    int trav = TRAV_LOCKSTEP;
-    bool twide = false;                    // the frame's scene has its 8-wide tree live (kernel template bit)
-    bool tuning = false;
     hipEvent_t tune_ev[16] = {};           // tuning frame: events around each spatial kernel (halo exchanges excluded)
-    int tune_n = 0;
     // tile-row dispatch order (rs_passes.h tile_of): per-row wave time of full-frame tuning frames, one
     // buffer per traversal kind; the chosen kind's costs order the 16-px tile rows, costliest first
     float* d_tune_cost[2] = {nullptr, nullptr};
-    int* d_order = nullptr;
-    int n_order = 0;
-    bool order_on = true;                  // RESTIR_TILE_ORDER=off: row-major dispatch
-    bool tune_rows = false;                // this tuning frame records per-row cost
-    // candidate-split initial pass (rs_passes.h k_gbuffer_initial_split): requested mode, last frame's
-    int split_mode = RS_SPLIT_AUTO;
-    bool split = false;
-    int wave_slots = 0;                    // resident wave capacity of the device at the initial pass's budget
+    int *d_order = nullptr, n_order = 0;
     // post-frame (rs_post_frame): accumulator (float3, like the reference's glm::vec3 accumulator),
     // display (float4 RGBA), per-workgroup statistic partials, accFrameCtr
     float* acc = nullptr;
     float4* display = nullptr;
-    double2* post_part = nullptr;
-    double2* post_out = nullptr;
+    double2 *post_part = nullptr, *post_out = nullptr;
     uint32_t acc_frames = 0;
     uint64_t post_px = 0;                  // pixels the last rs_post_frame's statistics cover
-    rs_camera cam_last = {};               // camera of the last frame (rs_export_png's sidecar)
     rs_denoiser* denoiser = nullptr;       // rs_post_frame's RenderParams::denoise (rs_context_set_denoiser)
     std::vector<rs_denoiser*> denoisers;   // every live denoiser created on this context (rs::ctx_track_denoiser)
-    // asynchronous framebuffer readback (rs_frame_readback): ticket ring, and per lane the readback its
-    // framebuffer is under (that lane's next frame waits for it before writing)
-    bool readback_kernel = false;          // DMA engine (default) or a copy kernel (env RESTIR_READBACK=kernel)
+    // asynchronous framebuffer readback (rs_frame_readback): ticket ring
     static constexpr int kRb = 8;
     hipEvent_t rb_ev[kRb] = {};
     bool rb_busy[kRb] = {};
     uint64_t rb_seq = 0;
-    hipEvent_t fb_read[kLanes] = {};
     hipEvent_t join_ev = nullptr;          // rs::ctx_join
     uint8_t* d_dbg = nullptr;              // debugReprojection marks (FrameConst::dbg), on first use
-    int cus = 256;
-    int sort_mode = RS_SPLIT_AUTO;         // wave-sorted initial pass (RESTIR_SORT=on|off; AUTO: per-lane walks)
-    bool sep_margin = true;                // a band's G-buffer margin rows in their own launch (RESTIR_MARGIN_SPLIT=off)
-    int sort_spatial = RS_SPLIT_AUTO;      // wave-sorted spatial pass, CONSTANT MIS, k <= 8 (RESTIR_SORT_SPATIAL=on|off;
-                                           // AUTO: per-lane walks -- C3 2.21 -> 1.87 ms; lockstep C5 0.228 -> 0.250)
-    int sort_temporal = RS_SPLIT_AUTO;     // wave-sorted temporal rays (RESTIR_SORT_TEMPORAL=off: per-ray walks)
-    bool light_lds = true;                 // the one-thread-per-pixel initial pass picks lights from an LDS copy of the
-                                           // tables when they fit (use_light_lds; RESTIR_LIGHT_LDS=off: global tables)
+    Lane& lane() { return lanes[fr.li]; }  // of the frame in flight / the last frame
 };
 
 // --------------------------------------------------------------------------- helpers
@@ -278,7 +271,7 @@ static hipError_t enter(rs_context* c) {
 // the context's stream and the run-ahead side streams
 static void sync_all(rs_context* c) {
     hipStreamSynchronize(c->stream);
-    for (auto st : c->lane) if (st) hipStreamSynchronize(st);
+    for (const Lane& L : c->lanes) if (L.stream) hipStreamSynchronize(L.stream);
 }
 
 // glm-semantics host maths for the camera (pg/camera.cpp:44-58, glm/ext/matrix_transform.inl:99-119,
@@ -349,6 +342,31 @@ static void make_camera(const rs_camera* c, int H, GCam& g, float inv3[9]) {
 }
 
 // --------------------------------------------------------------------------- context
+// the word of an on/off/auto switch: RS_SPLIT_ON / _OFF / _AUTO, or `other` for an unset variable or any other word
+static int env_word(const char* name, int other) {
+    const char* t = std::getenv(name);
+    if (!t) return other;
+    return !std::strcmp(t, "on") ? RS_SPLIT_ON : !std::strcmp(t, "off") ? RS_SPLIT_OFF : !std::strcmp(t, "auto") ? RS_SPLIT_AUTO : other;
+}
+// Every default is AUTO or on: a three-way switch takes on / off (auto is its default), a two-way one is on unless
+// `off`; unknown words leave the default.
+static Switches read_switches() {
+    Switches w;
+    if (const char* t = std::getenv("RESTIR_TRAVERSAL")) {     // auto (default) | lockstep | lane
+        if (!std::strcmp(t, "lockstep")) w.trav_mode = RS_TRAVERSAL_LOCKSTEP;
+        else if (!std::strcmp(t, "lane")) w.trav_mode = RS_TRAVERSAL_LANE;
+    }
+    w.split_mode = env_word("RESTIR_SPLIT", RS_SPLIT_AUTO);
+    w.persist_sorted = env_word("RESTIR_PERSIST_SORTED", RS_SPLIT_AUTO);
+    w.sort_mode = env_word("RESTIR_SORT", RS_SPLIT_AUTO);
+    w.sort_temporal = env_word("RESTIR_SORT_TEMPORAL", RS_SPLIT_AUTO);
+    w.sort_spatial = env_word("RESTIR_SORT_SPATIAL", RS_SPLIT_AUTO);
+    w.sep_margin = env_word("RESTIR_MARGIN_SPLIT", RS_SPLIT_ON) != RS_SPLIT_OFF;
+    w.light_lds = env_word("RESTIR_LIGHT_LDS", RS_SPLIT_ON) != RS_SPLIT_OFF;
+    w.order_on = env_word("RESTIR_TILE_ORDER", RS_SPLIT_ON) != RS_SPLIT_OFF;
+    if (const char* t = std::getenv("RESTIR_READBACK")) w.readback_kernel = std::strcmp(t, "kernel") == 0;   // sdma (default) | kernel
+    return w;
+}
 extern "C" int rs_context_create(int hip_device, int width, int height, void* hip_stream, rs_context** out) {
     if (!out || width <= 0 || height <= 0) return fail(nullptr, RS_E_INVALID, "rs_context_create: bad arguments");
     *out = nullptr;
@@ -365,8 +383,6 @@ extern "C" int rs_context_create(int hip_device, int width, int height, void* hi
         if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return bail("hipStreamCreate failed");
         c->own_stream = true;
     }
-    for (auto& st : c->lane)
-        if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return bail("hipStreamCreate failed");
     for (auto& h : c->rhist) h[0] = h[1] = h[2] = -1;
     size_t n = (size_t)width * height;
     for (int i = 0; i < kGRing; ++i) {
@@ -380,19 +396,20 @@ extern "C" int rs_context_create(int hip_device, int width, int height, void* hi
         if (hipMalloc(&c->R[i], n * 3 * sizeof(float4)) != hipSuccess) return bail("hipMalloc(reservoirs) failed");
         hipMemsetAsync(c->R[i], 0, n * 3 * sizeof(float4), c->stream);
     }
-    if (hipMalloc(&c->fbs[0], n * 3 * sizeof(float)) != hipSuccess) return bail("hipMalloc(frame) failed");
-    hipMemsetAsync(c->fbs[0], 0, n * 3 * sizeof(float), c->stream);
-    c->fb = c->fbs[0];
-    for (int i = 0; i < kLanes; ++i) {
-        if (hipMalloc(&c->cnts[i], sizeof(Counters)) != hipSuccess) return bail("hipMalloc(counters) failed");
-        if (hipMalloc(&c->reds[i], (kReduceBlocks + 1) * sizeof(ulonglong2)) != hipSuccess) return bail("hipMalloc(partials) failed");
-        hipMemsetAsync(c->reds[i], 0, (kReduceBlocks + 1) * sizeof(ulonglong2), c->stream);   // ticket = 0
-        hipMemsetAsync(c->cnts[i], 0, sizeof(Counters), c->stream);
-        if (hipMalloc(&c->qctr[i], 4 * sizeof(uint32_t)) != hipSuccess) return bail("hipMalloc(tile queues) failed");
-        hipMemsetAsync(c->qctr[i], 0, 4 * sizeof(uint32_t), c->stream);
+    for (Lane& L : c->lanes) {
+        if (hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking) != hipSuccess) return bail("hipStreamCreate failed");
+        if (&L == c->lanes) {
+            if (hipMalloc(&L.fb, n * 3 * sizeof(float)) != hipSuccess) return bail("hipMalloc(frame) failed");
+            hipMemsetAsync(L.fb, 0, n * 3 * sizeof(float), c->stream);
+        }
+        if (hipMalloc(&L.cnt, sizeof(Counters)) != hipSuccess) return bail("hipMalloc(counters) failed");
+        if (hipMalloc(&L.red, (kReduceBlocks + 1) * sizeof(ulonglong2)) != hipSuccess) return bail("hipMalloc(partials) failed");
+        hipMemsetAsync(L.red, 0, (kReduceBlocks + 1) * sizeof(ulonglong2), c->stream);   // ticket = 0
+        hipMemsetAsync(L.cnt, 0, sizeof(Counters), c->stream);
+        if (hipMalloc(&L.qctr, 4 * sizeof(uint32_t)) != hipSuccess) return bail("hipMalloc(tile queues) failed");
+        hipMemsetAsync(L.qctr, 0, 4 * sizeof(uint32_t), c->stream);
     }
-    c->d_cnt = c->cnts[0]; c->d_red = c->reds[0];
-    c->fs = c->stream;
+    c->fr.fs = c->stream;
     if (hipHostMalloc(&c->h_cnt, sizeof(Counters), hipHostMallocDefault) != hipSuccess) return bail("hipHostMalloc failed");
     if (hipMalloc(&c->d_tot, sizeof(Counters)) != hipSuccess) return bail("hipMalloc(totals) failed");
     hipMemsetAsync(c->d_tot, 0, sizeof(Counters), c->stream);
@@ -401,50 +418,14 @@ extern "C" int rs_context_create(int hip_device, int width, int height, void* hi
             if (hipEventCreate(&e) != hipSuccess) return bail("hipEventCreate failed");
     for (auto& e : c->ev_gt)
         if (hipEventCreate(&e) != hipSuccess) return bail("hipEventCreate failed");
-    for (int i = 0; i < EV_COUNT; ++i) c->ev[i] = c->evr[0][i];
+    c->fr.ev = c->evr[0];
     if (hipStreamSynchronize(c->stream) != hipSuccess) return bail("context init failed");
     rs::preload_code_objects();
-    if (const char* t = std::getenv("RESTIR_TRAVERSAL")) {     // auto (default) | lockstep | lane
-        if (!std::strcmp(t, "lockstep")) c->trav_mode = RS_TRAVERSAL_LOCKSTEP;
-        else if (!std::strcmp(t, "lane")) c->trav_mode = RS_TRAVERSAL_LANE;
-    }
-    if (const char* t = std::getenv("RESTIR_SPLIT")) {         // auto (default) | on | off
-        if (!std::strcmp(t, "on")) c->split_mode = RS_SPLIT_ON;
-        else if (!std::strcmp(t, "off")) c->split_mode = RS_SPLIT_OFF;
-    }
-    if (const char* t = std::getenv("RESTIR_PERSIST_SORTED")) {   // persistent-wave sorted pass: auto | on | off
-        if (!std::strcmp(t, "on")) c->persist_sorted = RS_SPLIT_ON;
-        else if (!std::strcmp(t, "off")) c->persist_sorted = RS_SPLIT_OFF;
-        else if (!std::strcmp(t, "auto")) c->persist_sorted = RS_SPLIT_AUTO;
-    }
-    if (const char* t = std::getenv("RESTIR_SORT")) {          // auto (default) | on | off: wave-sorted initial pass
-        if (!std::strcmp(t, "on")) c->sort_mode = RS_SPLIT_ON;
-        else if (!std::strcmp(t, "off")) c->sort_mode = RS_SPLIT_OFF;
-    }
-    if (const char* t = std::getenv("RESTIR_SORT_TEMPORAL")) { // auto (default) | on | off: wave-sorted temporal rays
-        if (!std::strcmp(t, "on")) c->sort_temporal = RS_SPLIT_ON;
-        else if (!std::strcmp(t, "off")) c->sort_temporal = RS_SPLIT_OFF;
-    }
-    if (const char* t = std::getenv("RESTIR_MARGIN_SPLIT"))    // on (default) | off
-        c->sep_margin = std::strcmp(t, "off") != 0;
-    if (const char* t = std::getenv("RESTIR_SORT_SPATIAL")) {  // auto (default) | on | off: wave-sorted spatial pass
-        if (!std::strcmp(t, "on")) c->sort_spatial = RS_SPLIT_ON;
-        else if (!std::strcmp(t, "off")) c->sort_spatial = RS_SPLIT_OFF;
-    }
-    if (const char* t = std::getenv("RESTIR_LIGHT_LDS"))       // auto (default) | off: light tables from global memory
-        c->light_lds = std::strcmp(t, "off") != 0;
-    if (const char* t = std::getenv("RESTIR_TILE_ORDER"))      // cost (default) | off (row-major)
-        c->order_on = std::strcmp(t, "off") != 0;
-    if (const char* t = std::getenv("RESTIR_READBACK"))        // sdma (default) | kernel
-        c->readback_kernel = std::strcmp(t, "kernel") == 0;
+    c->sw = read_switches();
     if (const char* t = std::getenv("RESTIR_RUNAHEAD"))        // run-ahead depth 0..kMaxAhead
         c->ahead = std::max(0, std::min(kMaxAhead, std::atoi(t)));
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) cus = 256;
-        c->wave_slots = cus * 4 * RS_INITIAL_WAVES;
-        c->cus = cus;
-    }
+    if (hipDeviceGetAttribute(&c->cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || c->cus <= 0) c->cus = 256;
+    c->wave_slots = c->cus * 4 * RS_INITIAL_WAVES;
     *out = c;
     return RS_OK;
 }
@@ -453,20 +434,20 @@ extern "C" int rs_context_set_traversal(rs_context* c, int mode) {
     if (!c) return fail(nullptr, RS_E_INVALID, "rs_context_set_traversal: null context");
     if (mode != RS_TRAVERSAL_AUTO && mode != RS_TRAVERSAL_LOCKSTEP && mode != RS_TRAVERSAL_LANE)
         return fail(c, RS_E_INVALID, "rs_context_set_traversal: mode must be RS_TRAVERSAL_AUTO/LOCKSTEP/LANE");
-    c->trav_mode = mode;
+    c->sw.trav_mode = mode;
     return RS_OK;
 }
 extern "C" int rs_context_set_initial_split(rs_context* c, int mode) {
     if (!c) return fail(nullptr, RS_E_INVALID, "rs_context_set_initial_split: null context");
     if (mode != RS_SPLIT_AUTO && mode != RS_SPLIT_OFF && mode != RS_SPLIT_ON)
         return fail(c, RS_E_INVALID, "rs_context_set_initial_split: mode must be RS_SPLIT_AUTO/OFF/ON");
-    c->split_mode = mode;
+    c->sw.split_mode = mode;
     return RS_OK;
 }
 extern "C" int rs_max_run_ahead(void) { return kMaxAhead; }
 extern "C" int rs_context_set_run_ahead(rs_context* c, int depth) {
     if (!c) return fail(nullptr, RS_E_INVALID, "rs_context_set_run_ahead: null context");
-    if (c->active) return fail(c, RS_E_INVALID, "rs_context_set_run_ahead: a frame is in flight");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_context_set_run_ahead: a frame is in flight");
     HIPCHK(c, enter(c));
     sync_all(c);                                 // frames in flight keep the buffers of the old depth
     if (depth < 0 || depth > kMaxAhead) return fail(c, RS_E_INVALID, "rs_context_set_run_ahead: depth must be 0.." + std::to_string(kMaxAhead));
@@ -477,7 +458,7 @@ extern "C" int rs_context_set_run_ahead(rs_context* c, int depth) {
 extern "C" int rs_context_handoff_bytes(const rs_context* c, uint64_t* bytes) {
     if (!c || !bytes) return RS_E_INVALID;
     uint64_t b = 0;
-    for (size_t s : c->cand_slots) b += (uint64_t)s * (uint64_t)(kSortChunk * 64) * (sizeof(float) + sizeof(float4));
+    for (const Lane& L : c->lanes) b += (uint64_t)L.cand_slots * (uint64_t)(kSortChunk * 64) * (sizeof(float) + sizeof(float4));
     *bytes = b;
     return RS_OK;
 }
@@ -485,14 +466,14 @@ extern "C" int rs_context_handoff_bytes(const rs_context* c, uint64_t* bytes) {
 extern "C" int rs_context_set_frame_ring(rs_context* c, int n) {
     if (!c) return fail(nullptr, RS_E_INVALID, "rs_context_set_frame_ring: null context");
     if (n != 1 && n != 2) return fail(c, RS_E_INVALID, "rs_context_set_frame_ring: n must be 1 or 2");
-    if (c->active) return fail(c, RS_E_INVALID, "rs_context_set_frame_ring: a frame is in flight");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_context_set_frame_ring: a frame is in flight");
     HIPCHK(c, enter(c));
     c->fb_ring = n;
     return RS_OK;
 }
 extern "C" int rs_context_track_row_costs(rs_context* c, int enable) {
     if (!c) return fail(nullptr, RS_E_INVALID, "rs_context_track_row_costs: null context");
-    if (c->active) return fail(c, RS_E_INVALID, "rs_context_track_row_costs: a frame is in flight");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_context_track_row_costs: a frame is in flight");
     HIPCHK(c, enter(c));
     if (enable && !c->d_rowcost) {
         HIPCHK(c, hipMalloc(&c->d_rowcost, (size_t)c->H * sizeof(float)));
@@ -503,7 +484,7 @@ extern "C" int rs_context_track_row_costs(rs_context* c, int enable) {
 }
 extern "C" int rs_get_row_costs(rs_context* c, float* costs, int reset) {
     if (!c || !costs) return fail(c, RS_E_INVALID, "rs_get_row_costs: null argument");
-    if (c->active) return fail(c, RS_E_INVALID, "rs_get_row_costs: a frame is in flight");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_get_row_costs: a frame is in flight");
     HIPCHK(c, enter(c));
     const size_t bytes = (size_t)c->H * sizeof(float);
     if (!c->d_rowcost) { std::memset(costs, 0, bytes); return RS_OK; }
@@ -514,15 +495,15 @@ extern "C" int rs_get_row_costs(rs_context* c, float* costs, int reset) {
 }
 extern "C" int rs_context_get_initial_split(const rs_context* c, int* mode, int* last) {
     if (!c) return fail(nullptr, RS_E_INVALID, "rs_context_get_initial_split: null context");
-    if (mode) *mode = c->split_mode;
-    if (last) *last = c->split ? 1 : 0;
+    if (mode) *mode = c->sw.split_mode;
+    if (last) *last = c->fr.split ? 1 : 0;
     return RS_OK;
 }
 extern "C" int rs_context_get_traversal(const rs_context* c, const rs_scene* s, int* mode, int* last_kind,
                                         int* scene_choice) {
     if (!c) return fail(nullptr, RS_E_INVALID, "rs_context_get_traversal: null context");
-    if (mode) *mode = c->trav_mode;
-    if (last_kind) *last_kind = c->trav;
+    if (mode) *mode = c->sw.trav_mode;
+    if (last_kind) *last_kind = c->fr.trav;
     if (scene_choice) *scene_choice = s ? s->trav_choice : -1;
     return RS_OK;
 }
@@ -531,7 +512,7 @@ extern "C" void rs_context_destroy(rs_context* c) {
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    for (auto st : c->lane) if (st) hipStreamSynchronize(st);
+    for (const Lane& L : c->lanes) if (L.stream) hipStreamSynchronize(L.stream);
     for (rs_denoiser* d : c->denoisers) rs::denoiser_detach(d);   // their rs_denoiser_destroy frees the rest
     for (auto e : c->rb_ev) if (e) hipEventDestroy(e);
     if (c->join_ev) hipEventDestroy(c->join_ev);
@@ -540,25 +521,18 @@ extern "C" void rs_context_destroy(rs_context* c) {
         for (auto* p : f) if (p) hipFree(p);
     }
     for (auto* r : c->R) if (r) hipFree(r);
-    for (float* f : c->fbs) if (f) hipFree(f);
-    if (c->d_rowcost) hipFree(c->d_rowcost);
-    for (auto* p : c->cnts) if (p) hipFree(p);
-    for (auto* p : c->reds) if (p) hipFree(p);
-    for (auto* p : c->qctr) if (p) hipFree(p);
-    for (auto* p : c->candw) if (p) hipFree(p);
-    for (auto* p : c->candr) if (p) hipFree(p);
-    if (c->d_tot) hipFree(c->d_tot);
-    void* post[] = {c->acc, c->display, c->post_part, c->post_out};
-    for (void* p : post) if (p) hipFree(p);
-    for (uint2* p : c->parts) if (p) hipFree(p);
+    void* own[] = {c->d_rowcost, c->d_tot, c->acc, c->display, c->post_part, c->post_out, c->d_order, c->d_tune_cost[0], c->d_tune_cost[1]};
+    for (void* p : own) if (p) hipFree(p);
     if (c->h_cnt) hipHostFree(c->h_cnt);
     for (auto& slot : c->evr)
         for (auto& e : slot) if (e) hipEventDestroy(e);
     for (auto& e : c->ev_gt) if (e) hipEventDestroy(e);
     for (auto& e : c->tune_ev) if (e) hipEventDestroy(e);
-    for (float* p : c->d_tune_cost) if (p) hipFree(p);
-    if (c->d_order) hipFree(c->d_order);
-    for (auto st : c->lane) if (st) hipStreamDestroy(st);
+    for (Lane& L : c->lanes) {
+        void* own[] = {L.fb, L.cnt, L.red, L.part, L.qctr, L.candw, L.candr};
+        for (void* p : own) if (p) hipFree(p);
+        if (L.stream) hipStreamDestroy(L.stream);
+    }
     if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
@@ -569,6 +543,7 @@ extern "C" const char* rs_last_error(const rs_context* c) {
 
 // --------------------------------------------------------------------------- scene
 static int build_geometry(rs_context* c, rs_scene* s, const std::vector<float>& pos, std::string& err);
+static void geo_free(GeoCopy& g);
 // Utils::expand (pg/utils.cpp:209-218)
 static float srgb_expand1(float u) {
     if (u <= 0.0f) return 0.0f;
@@ -842,53 +817,40 @@ static int build_geometry(rs_context* c, rs_scene* s, const std::vector<float>& 
     c->join_next = true;
     sync_all(c);                                // frames in flight, pipelined updates
     if (hipStreamSynchronize(st) != hipSuccess) { err = "stream sync failed"; return -1; }
-    {
-        void* alt[] = {s->a_nodes, s->a_tris, s->a_emis, s->a_cdf, s->a_cdf_guide, s->a_tri_nrm};
-        for (void* p : alt) if (p) hipFree(p);
-        wide_free(s->a_wide);
-        s->a_nodes = s->a_tris = s->a_emis = s->a_tri_nrm = nullptr; s->a_cdf = nullptr; s->a_cdf_guide = nullptr;
-        s->a_geo = 0xffffffffu; s->a_nrm = false;
-        s->update_recorded = false;
-    }
-    void* old[] = {s->d_pos, s->d_nodes, s->d_tris, s->d_emis, s->d_cdf, s->d_cdf_guide, s->d_emis_tri,
-                   s->d_refit_order, s->d_refit_lvl, s->d_ebucket};
-    s->d_ebucket = nullptr;
-    wide_free(s->wide); s->wide_on = false;
+    geo_free(s->alt);
+    if (s->a_tri_nrm) hipFree(s->a_tri_nrm);
+    s->a_tri_nrm = nullptr; s->a_geo = 0xffffffffu; s->a_nrm = false;
+    s->update_recorded = false;
+    geo_free(s->geo); s->wide_on = false;
+    void* old[] = {s->d_pos, s->d_emis_tri, s->d_refit_order, s->d_refit_lvl, s->d_ebucket};
     for (void* p : old) if (p) hipFree(p);
-    s->d_pos = nullptr; s->d_nodes = nullptr; s->d_tris = nullptr; s->d_emis = nullptr; s->d_cdf = nullptr;
-    s->d_cdf_guide = nullptr; s->d_emis_tri = nullptr; s->d_refit_order = nullptr; s->d_refit_lvl = nullptr;
+    s->d_pos = nullptr; s->d_ebucket = nullptr; s->d_emis_tri = nullptr; s->d_refit_order = nullptr; s->d_refit_lvl = nullptr;
     s->n_nodes = 0; s->refit_lvl.clear();
     s->n_emis = ne;
-    if (n) {
-        if (hipMalloc(&s->d_pos, pos.size() * sizeof(float)) != hipSuccess) { err = "hipMalloc(pos) failed"; return -1; }
-        hipMemcpyAsync(s->d_pos, pos.data(), pos.size() * sizeof(float), hipMemcpyHostToDevice, st);
-    }
-    if (hipMalloc(&s->d_emis, em.size() * sizeof(float4)) != hipSuccess) { err = "hipMalloc(emis) failed"; return -1; }
-    hipMemcpyAsync(s->d_emis, em.data(), em.size() * sizeof(float4), hipMemcpyHostToDevice, st);
-    if (hipMalloc(&s->d_cdf, cdf.size() * sizeof(float)) != hipSuccess) { err = "hipMalloc(cdf) failed"; return -1; }
-    hipMemcpyAsync(s->d_cdf, cdf.data(), cdf.size() * sizeof(float), hipMemcpyHostToDevice, st);
-    if (hipMalloc(&s->d_cdf_guide, guide.size() * sizeof(int)) != hipSuccess) { err = "hipMalloc(guide) failed"; return -1; }
-    hipMemcpyAsync(s->d_cdf_guide, guide.data(), guide.size() * sizeof(int), hipMemcpyHostToDevice, st);
-    if (hipMalloc(&s->d_ebucket, ebucket.size()) != hipSuccess) { err = "hipMalloc(emitter buckets) failed"; return -1; }
-    hipMemcpyAsync(s->d_ebucket, ebucket.data(), ebucket.size(), hipMemcpyHostToDevice, st);
-    if (ne) {
-        if (hipMalloc(&s->d_emis_tri, ne * sizeof(int)) != hipSuccess) { err = "hipMalloc(emis ids) failed"; return -1; }
-        hipMemcpyAsync(s->d_emis_tri, emis_tri.data(), ne * sizeof(int), hipMemcpyHostToDevice, st);
-    }
+    auto upload = [&](auto** d, const void* h, size_t bytes, const char* what) {
+        if (hipMalloc(d, bytes) != hipSuccess) { err = std::string("hipMalloc(") + what + ") failed"; return false; }
+        hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, st);
+        return true;
+    };
+    if ((n && !upload(&s->d_pos, pos.data(), pos.size() * sizeof(float), "pos")) ||
+        !upload(&s->geo.emis, em.data(), em.size() * sizeof(float4), "emis") || !upload(&s->geo.cdf, cdf.data(), cdf.size() * sizeof(float), "cdf") ||
+        !upload(&s->geo.cdf_guide, guide.data(), guide.size() * sizeof(int), "guide") ||
+        !upload(&s->d_ebucket, ebucket.data(), ebucket.size(), "emitter buckets") ||
+        (ne && !upload(&s->d_emis_tri, emis_tri.data(), ne * sizeof(int), "emis ids"))) return -1;
     if (hipStreamSynchronize(st) != hipSuccess) { err = "geometry upload failed"; return -1; }   // host vectors die
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
     hipEventRecord(e0, st);
     std::string berr;
     s->box_eps = box_epsilon(pos.data(), pos.size());
-    int rc = build_bvh(s->d_pos, n, st, &s->d_nodes, &s->n_nodes, &s->d_tris, &s->wide, berr);
-    s->wide_on = rc == 0 && s->wide.n_nodes > 0 && s->wide.depth <= kWideStack;   // deeper: the skip pointers
+    int rc = build_bvh(s->d_pos, n, st, &s->geo.nodes, &s->n_nodes, &s->geo.tris, &s->geo.wide, berr);
+    s->wide_on = rc == 0 && s->geo.wide.n_nodes > 0 && s->geo.wide.depth <= kWideStack;   // deeper: the skip pointers
     hipEventRecord(e1, st);
     if (rc == 0 && hipStreamSynchronize(st) == hipSuccess) hipEventElapsedTime(&s->build_ms, e0, e1);
     else { err = "BVH build failed: " + berr; rc = -1; (void)hipStreamSynchronize(st); }
     builder_pool_trim();                          // the build's scratch back to the driver (stream drained above)
     hipEventDestroy(e0); hipEventDestroy(e1);
-    if (rc == 0 && bvh_refit_plan(s->d_nodes, s->n_nodes, st, &s->d_refit_order, &s->d_refit_lvl, s->refit_lvl, berr) != 0) {
+    if (rc == 0 && bvh_refit_plan(s->geo.nodes, s->n_nodes, st, &s->d_refit_order, &s->d_refit_lvl, s->refit_lvl, berr) != 0) {
         err = berr; rc = -1;
     }
     return rc;
@@ -1021,6 +983,33 @@ static int wide_copy(rs_context* c, const WideBvh& from, WideBvh& to, hipStream_
     return RS_OK;
 }
 
+// a GeoCopy's buffers from sizes (its 8-wide tree comes with the first geo_copy: wide_copy)
+static int geo_alloc(rs_context* c, GeoCopy& g, const GeoBytes& b) {
+    HIPCHK(c, hipMalloc(&g.nodes, b.nodes));
+    HIPCHK(c, hipMalloc(&g.tris, b.tris));
+    HIPCHK(c, hipMalloc(&g.emis, std::max<size_t>(b.emis, sizeof(float4))));
+    HIPCHK(c, hipMalloc(&g.cdf, b.cdf));
+    HIPCHK(c, hipMalloc(&g.cdf_guide, b.guide));
+    return RS_OK;
+}
+// device-to-device on `st`: the trees (the 8-wide one when live), and with `tables` the light tables
+static int geo_copy(rs_context* c, const GeoCopy& from, GeoCopy& to, const GeoBytes& b, bool wide, bool tables, hipStream_t st) {
+    HIPCHK(c, hipMemcpyAsync(to.nodes, from.nodes, b.nodes, hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(to.tris, from.tris, b.tris, hipMemcpyDeviceToDevice, st));
+    if (tables) {
+        if (b.emis) HIPCHK(c, hipMemcpyAsync(to.emis, from.emis, b.emis, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(to.cdf, from.cdf, b.cdf, hipMemcpyDeviceToDevice, st));
+        HIPCHK(c, hipMemcpyAsync(to.cdf_guide, from.cdf_guide, b.guide, hipMemcpyDeviceToDevice, st));
+    }
+    return wide ? wide_copy(c, from.wide, to.wide, st) : RS_OK;
+}
+static void geo_free(GeoCopy& g) {
+    void* own[] = {g.nodes, g.tris, g.emis, g.cdf, g.cdf_guide};
+    for (void* p : own) if (p) hipFree(p);
+    wide_free(g.wide);
+    g.nodes = g.tris = g.emis = nullptr; g.cdf = nullptr; g.cdf_guide = nullptr;
+}
+
 __global__ void k_set_normals(const float* __restrict__ nrm, uint32_t n, float4* tri_nrm) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n) return;
@@ -1041,15 +1030,14 @@ __global__ void k_set_normals(const float* __restrict__ nrm, uint32_t n, float4*
 extern "C" int rs_scene_update_positions(rs_scene* s, const float* positions, const float* normals) {
     if (!s || !positions) return fail(s ? s->ctx : nullptr, RS_E_INVALID, "rs_scene_update_positions: null argument");
     rs_context* c = s->ctx;
-    if (c->active) return fail(c, RS_E_INVALID, "rs_scene_update_positions: a frame is in flight");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_scene_update_positions: a frame is in flight");
     HIPCHK(c, enter(c));
     const size_t nf = 9 * (size_t)s->n_tris;
     if (nf == 0) return RS_OK;
     // frames in flight and positions only (no normals): pipelined into the other
     // scene copy; otherwise in place after every enqueued frame (the next frame joins the context stream)
     const bool pipelined = c->ahead > 0 && !normals;
-    const int L = c->ahead > 0 ? (int)(c->seq % (uint64_t)(c->ahead + 1)) : 0;
-    hipStream_t st = pipelined ? c->lane[L] : c->stream;
+    hipStream_t st = pipelined ? c->lanes[ring::lane_of(c->seq, c->ahead, c->fb_ring)].stream : c->stream;   // the next frame's lane
     const int k = s->stage_i;
     s->stage_i ^= 1;
     if (!s->h_stage[k]) {
@@ -1061,45 +1049,29 @@ extern "C" int rs_scene_update_positions(rs_scene* s, const float* positions, co
     std::memcpy(s->h_stage[k], positions, nf * sizeof(float));
     if (!s->update_ev) HIPCHK(c, hipEventCreateWithFlags(&s->update_ev, hipEventDisableTiming));
     if (s->update_recorded) HIPCHK(c, hipStreamWaitEvent(st, s->update_ev, 0));   // d_pos and the copies
-    float4 *nodes = s->d_nodes, *tris = s->d_tris, *em = s->d_emis;
-    float* cdf = s->d_cdf;
-    int* guide = s->d_cdf_guide;
-    const size_t bn = 2 * ((size_t)s->n_nodes + 1) * sizeof(float4), bt = 3 * (size_t)s->n_tris * sizeof(float4),
-                 be = 8 * (size_t)s->n_emis * sizeof(float4), bc = (size_t)std::max(1u, s->n_emis) * sizeof(float),
-                 bg = (kCdfGuide + 1) * sizeof(int), bnrm = 3 * (size_t)s->n_tris * sizeof(float4);
-    if (!s->a_nodes) {                           // the second copy, on first use: topology and tables copied
+    const GeoBytes gb = s->geo_bytes();
+    if (!s->alt.nodes) {                         // the second copy, on first use: topology and tables copied
         sync_all(c);
-        HIPCHK(c, hipMalloc(&s->a_nodes, bn));
-        HIPCHK(c, hipMalloc(&s->a_tris, bt));
-        HIPCHK(c, hipMalloc(&s->a_emis, std::max<size_t>(be, sizeof(float4))));
-        HIPCHK(c, hipMalloc(&s->a_cdf, bc));
-        HIPCHK(c, hipMalloc(&s->a_cdf_guide, bg));
-        HIPCHK(c, hipMemcpyAsync(s->a_nodes, s->d_nodes, bn, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(s->a_tris, s->d_tris, bt, hipMemcpyDeviceToDevice, st));
-        if (be) HIPCHK(c, hipMemcpyAsync(s->a_emis, s->d_emis, be, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(s->a_cdf, s->d_cdf, bc, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(s->a_cdf_guide, s->d_cdf_guide, bg, hipMemcpyDeviceToDevice, st));
-        if (s->wide_on) if (int rc = wide_copy(c, s->wide, s->a_wide, st)) return rc;
+        if (int rc = geo_alloc(c, s->alt, gb)) return rc;
+        if (int rc = geo_copy(c, s->geo, s->alt, gb, s->wide_on, true, st)) return rc;
     }
-    WideBvh* wt = &s->wide;                      // the 8-wide tree the refit writes
+    GeoCopy* to = &s->geo;                       // the copy the refits (both trees) and the light tables write
     if (pipelined) {
         // every frame that read the copy about to be written has finished (a lane's frames in stream order):
         // the frames of that generation, and tile frames that rebuilt elements from it as the previous one
-        for (int l = 0; l < kLanes; ++l)
-            if (c->lane_scene[l] == s && (((s->gen - c->lane_gen[l]) & 1) || c->lane_prevgeo[l]) && c->lane_done[l])
-                HIPCHK(c, hipStreamWaitEvent(st, c->lane_done[l], 0));
-        nodes = s->a_nodes; tris = s->a_tris; em = s->a_emis; cdf = s->a_cdf; guide = s->a_cdf_guide;
-        wt = &s->a_wide;
+        for (const Lane& L : c->lanes)
+            if (L.scene == s && (((s->gen - L.gen) & 1) || L.prevgeo) && L.done)
+                HIPCHK(c, hipStreamWaitEvent(st, L.done, 0));
+        to = &s->alt;
         s->a_nrm = false;
     } else {
         c->join_next = true;                     // the next frame's initial pass must see the new geometry
-        // in place (after every enqueued frame): the current geometry becomes the a_* copy first, so a
+        // in place (after every enqueued frame): the current geometry becomes the alt copy first, so a
         // tile's next temporal pass can still trace the previous frame's geometry
-        HIPCHK(c, hipMemcpyAsync(s->a_nodes, s->d_nodes, bn, hipMemcpyDeviceToDevice, st));
-        HIPCHK(c, hipMemcpyAsync(s->a_tris, s->d_tris, bt, hipMemcpyDeviceToDevice, st));
-        if (s->wide_on) if (int rc = wide_copy(c, s->wide, s->a_wide, st)) return rc;
+        if (int rc = geo_copy(c, s->geo, s->alt, gb, s->wide_on, false, st)) return rc;
         s->a_nrm = normals != nullptr;
         if (s->a_nrm) {
+            const size_t bnrm = 3 * (size_t)s->n_tris * sizeof(float4);
             if (!s->a_tri_nrm) HIPCHK(c, hipMalloc(&s->a_tri_nrm, bnrm));
             HIPCHK(c, hipMemcpyAsync(s->a_tri_nrm, s->d_tri_nrm, bnrm, hipMemcpyDeviceToDevice, st));
         }
@@ -1117,31 +1089,30 @@ extern "C" int rs_scene_update_positions(rs_scene* s, const float* positions, co
     HIPCHK(c, hipEventRecord(s->stage_ev[k], st));
     std::string err;
     int tail[2];
-    if (bvh_refit(nodes, tris, s->d_pos, s->d_refit_order, s->d_refit_lvl, s->refit_lvl, st, tail, err) != 0)
+    if (bvh_refit(to->nodes, to->tris, s->d_pos, s->d_refit_order, s->d_refit_lvl, s->refit_lvl, st, tail, err) != 0)
         return fail(c, RS_E_HIP, "rs_scene_update_positions: " + err);
-    RefitArgs R{nodes, tris, s->d_pos, s->d_refit_order, s->d_refit_lvl, tail[0], tail[1]};
+    RefitArgs R{to->nodes, to->tris, s->d_pos, s->d_refit_order, s->d_refit_lvl, tail[0], tail[1]};
     // the 8-wide tree keeps its topology and is refit too (rs_refit.h): large levels alone, the last run of
     // small levels up to the root in the fused launch's third workgroup
-    WideRefitArgs W = wide_refit_args(*wt, s->d_pos, -1, 0);
+    WideRefitArgs W = wide_refit_args(to->wide, s->d_pos, -1, 0);
     if (s->wide_on) {
-        const std::vector<WideBatch> wb = wide_refit_batches(*wt);
+        const std::vector<WideBatch> wb = wide_refit_batches(to->wide);
         for (size_t i = 0; i < wb.size(); ++i) {
             if (i + 1 == wb.size() && wb[i].blocks == 1) { W.l_deep = wb[i].l_deep; W.l_top = wb[i].l_top; break; }
-            WideRefitArgs A = wide_refit_args(*wt, s->d_pos, wb[i].l_deep, wb[i].l_top);
+            WideRefitArgs A = wide_refit_args(to->wide, s->d_pos, wb[i].l_deep, wb[i].l_top);
             k_wide_refit<<<wb[i].blocks, kRefitBlock, 0, st>>>(A);
         }
     }
     // the light tables, the binary refit's last levels and the wide refit's last levels, one workgroup each
-    k_scene_update<<<3, kLightBlock, 0, st>>>(s->d_pos, s->d_tri_nrm, s->d_mats, s->d_emis_tri, s->n_emis, em, cdf, guide,
-                                              R, W);
+    k_scene_update<<<3, kLightBlock, 0, st>>>(s->d_pos, s->d_tri_nrm, s->d_mats, s->d_emis_tri, s->n_emis, to->emis, to->cdf,
+                                              to->cdf_guide, R, W);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(s->update_ev, st));
     s->update_recorded = true;
     if (pipelined) {                             // later frames read the new copy
-        std::swap(s->d_nodes, s->a_nodes); std::swap(s->d_tris, s->a_tris); std::swap(s->d_emis, s->a_emis);
-        std::swap(s->d_cdf, s->a_cdf); std::swap(s->d_cdf_guide, s->a_cdf_guide);
-        // (a scene without a live wide tree has no second copy: s->wide keeps the reason, rs_scene_walk_info)
-        if (s->wide_on) std::swap(s->wide, s->a_wide);
+        std::swap(s->geo, s->alt);
+        // (a scene without a live wide tree has no second copy: geo.wide keeps the reason, rs_scene_walk_info)
+        if (!s->wide_on) std::swap(s->geo.wide, s->alt.wide);
         s->gen++;
     }
     return RS_OK;
@@ -1152,7 +1123,7 @@ extern "C" int rs_scene_update_positions(rs_scene* s, const float* positions, co
 extern "C" int rs_scene_rebuild(rs_scene* s) {
     if (!s) return fail(nullptr, RS_E_INVALID, "rs_scene_rebuild: null scene");
     rs_context* c = s->ctx;
-    if (c->active) return fail(c, RS_E_INVALID, "rs_scene_rebuild: a frame is in flight");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_scene_rebuild: a frame is in flight");
     HIPCHK(c, enter(c));
     std::vector<float> pos(9 * (size_t)s->n_tris);
     if (!pos.empty()) {
@@ -1231,7 +1202,7 @@ extern "C" int rs_scene_load_obj(rs_context* c, const char* path, rs_scene** out
 extern "C" int rs_scene_set_sky(rs_scene* s, const rs_texture_desc* d) {
     if (!s) return fail(nullptr, RS_E_INVALID, "rs_scene_set_sky: null scene");
     rs_context* c = s->ctx;
-    if (c->active) return fail(c, RS_E_INVALID, "rs_scene_set_sky: a frame is in flight");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_scene_set_sky: a frame is in flight");
     HIPCHK(c, enter(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));        // enqueued frames may still read the texture buffer
     c->join_next = true;
@@ -1275,20 +1246,27 @@ extern "C" void rs_scene_destroy(rs_scene* s) {
     if (s->ctx) hipSetDevice(s->ctx->device);
     if (s->ctx && s->ctx->stream) hipStreamSynchronize(s->ctx->stream);
     if (s->ctx) sync_all(s->ctx);
-    void* ptrs[] = {s->d_pos, s->d_nodes, s->d_tris, s->d_tri_nrm, s->d_mats, s->d_emis, s->d_cdf, s->d_cdf_guide,
-                    s->d_emis_tri, s->d_refit_order, s->d_refit_lvl, s->d_nrm_stage, s->d_tex, s->d_texd, s->d_uv,
-                    s->d_tan, s->a_tri_nrm, s->a_nodes, s->a_tris, s->a_emis, s->a_cdf, s->a_cdf_guide, s->d_ebucket};
+    void* ptrs[] = {s->d_pos, s->d_tri_nrm, s->d_mats, s->d_emis_tri, s->d_refit_order, s->d_refit_lvl, s->d_nrm_stage,
+                    s->d_tex, s->d_texd, s->d_uv, s->d_tan, s->a_tri_nrm, s->d_ebucket};
     for (void* p : ptrs) if (p) hipFree(p);
-    wide_free(s->wide);
-    wide_free(s->a_wide);
+    geo_free(s->geo);
+    geo_free(s->alt);
     for (int k = 0; k < 2; ++k) {
         if (s->h_stage[k]) hipHostFree(s->h_stage[k]);
         if (s->stage_ev[k]) hipEventDestroy(s->stage_ev[k]);
     }
     if (s->update_ev) hipEventDestroy(s->update_ev);
-    {
-    }
     delete s;
+}
+
+// the end of a tree dump: the primitive id of each leaf triangle (the .w of its first float4) if asked for; the
+// context's stream, with the copies enqueued before, is synchronised either way
+static int read_prims(rs_context* c, const float4* tris, uint32_t n, int32_t* prims) {
+    std::vector<float4> t(prims ? 3 * (size_t)n : 0);
+    if (prims) HIPCHK(c, hipMemcpyAsync(t.data(), tris, t.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < t.size() / 3; ++k) std::memcpy(&prims[k], &t[3 * k].w, 4);
+    return RS_OK;
 }
 
 extern "C" int rs_debug_wide_tree(const rs_scene* s, uint32_t* n_nodes, uint32_t* n_tris, int32_t* depth, uint32_t* words,
@@ -1296,7 +1274,7 @@ extern "C" int rs_debug_wide_tree(const rs_scene* s, uint32_t* n_nodes, uint32_t
     if (!s || !n_nodes || !n_tris) return fail(s ? s->ctx : nullptr, RS_E_INVALID, "rs_debug_wide_tree: null argument");
     rs_context* c = s->ctx;
     HIPCHK(c, enter(c));
-    const WideBvh& w = s->wide;
+    const WideBvh& w = s->geo.wide;
     const bool on = s->wide_on && w.nodes;
     *n_nodes = on ? w.n_nodes : 0u;
     *n_tris = on ? w.n_tris : 0u;
@@ -1304,44 +1282,29 @@ extern "C" int rs_debug_wide_tree(const rs_scene* s, uint32_t* n_nodes, uint32_t
     if (!on || (!words && !prims)) return RS_OK;
     if (s->update_recorded) HIPCHK(c, hipStreamWaitEvent(c->stream, s->update_ev, 0));
     if (words) HIPCHK(c, hipMemcpyAsync(words, w.nodes, (size_t)w.n_nodes * 5 * sizeof(uint4), hipMemcpyDeviceToHost, c->stream));
-    std::vector<float4> t;
-    if (prims) {
-        t.resize(3 * (size_t)w.n_tris);
-        HIPCHK(c, hipMemcpyAsync(t.data(), w.tris, t.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (prims)
-        for (uint32_t k = 0; k < w.n_tris; ++k) std::memcpy(&prims[k], &t[3 * (size_t)k].w, 4);
-    return RS_OK;
+    return read_prims(c, w.tris, w.n_tris, prims);
 }
 
 extern "C" int rs_debug_bvh_tree(const rs_scene* s, uint32_t* n_nodes, uint32_t* n_tris, float* nodes, int32_t* prims) {
     if (!s || !n_nodes || !n_tris) return fail(s ? s->ctx : nullptr, RS_E_INVALID, "rs_debug_bvh_tree: null argument");
     rs_context* c = s->ctx;
     HIPCHK(c, enter(c));
-    const bool on = s->d_nodes && s->d_tris && s->n_nodes;
+    const bool on = s->geo.nodes && s->geo.tris && s->n_nodes;
     *n_nodes = on ? s->n_nodes : 0u;
     *n_tris = on ? s->n_tris : 0u;
     if (!on || (!nodes && !prims)) return RS_OK;
     if (s->update_recorded) HIPCHK(c, hipStreamWaitEvent(c->stream, s->update_ev, 0));   // a pipelined update
-    if (nodes) HIPCHK(c, hipMemcpyAsync(nodes, s->d_nodes, (size_t)s->n_nodes * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    std::vector<float4> t;
-    if (prims) {
-        t.resize(3 * (size_t)s->n_tris);
-        HIPCHK(c, hipMemcpyAsync(t.data(), s->d_tris, t.size() * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (prims)
-        for (uint32_t k = 0; k < s->n_tris; ++k) std::memcpy(&prims[k], &t[3 * (size_t)k].w, 4);
-    return RS_OK;
+    if (nodes) HIPCHK(c, hipMemcpyAsync(nodes, s->geo.nodes, (size_t)s->n_nodes * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    return read_prims(c, s->geo.tris, s->n_tris, prims);
 }
 
 extern "C" int rs_scene_walk_info(const rs_scene* s, uint32_t* wide_nodes, int32_t* wide_depth, int32_t* status) {
     if (!s) return fail(nullptr, RS_E_INVALID, "rs_scene_walk_info: null scene");
-    const bool on = s->wide_on && s->wide.nodes;
-    if (wide_nodes) *wide_nodes = on ? s->wide.n_nodes : 0u;
-    if (wide_depth) *wide_depth = on ? s->wide.depth : -1;
-    if (status) *status = on ? RS_WIDE_LIVE : (s->wide.status ? s->wide.status : RS_WIDE_TOO_DEEP);
+    const WideBvh& w = s->geo.wide;
+    const bool on = s->wide_on && w.nodes;
+    if (wide_nodes) *wide_nodes = on ? w.n_nodes : 0u;
+    if (wide_depth) *wide_depth = on ? w.depth : -1;
+    if (status) *status = on ? RS_WIDE_LIVE : (w.status ? w.status : RS_WIDE_TOO_DEEP);
     return RS_OK;
 }
 
@@ -1356,15 +1319,18 @@ extern "C" int rs_scene_info(const rs_scene* s, uint32_t* n_tris, uint32_t* n_em
 }
 
 // --------------------------------------------------------------------------- frame / tile driver
-static dim3 grid_rows(int W, int ya, int yb) { return dim3((W + 15) / 16, (yb - ya + 15) / 16); }
+// launch grids and their waves (rs_frame_ring.h)
+static dim3 grid_rows(int W, int ya, int yb) { const ring::Grid g = ring::grid_rows(W, ya, yb); return dim3(g.x, g.y); }
+static dim3 grid_split(int W, int ya, int yb) { const ring::Grid g = ring::grid_split(W, ya, yb); return dim3(g.x, g.y); }
+static size_t grid_waves(dim3 g, int waves_per_block = 4) { return ring::grid_waves({g.x, g.y}, waves_per_block); }
 
 // The kernel instantiation of the frame: walk kind | TRAV_WIDE when the scene's 8-wide tree is live (rs_scene.h Trav;
-// c->twide is taken from the scene when the frame begins).  The one switch over the kind: f gets it as a compile-time
+// fr.twide is taken from the scene when the frame begins).  The one switch over the kind: f gets it as a compile-time
 // constant T (T() in a template argument) and names the kernel, its own variant bits, grid, block, LDS and stream.
 template <int T> using Kind = std::integral_constant<int, T>;
 template <class Fn>
 static auto with_trav(const rs_context* c, Fn&& f) {
-    switch (c->trav | (c->twide ? TRAV_WIDE : 0)) {
+    switch (c->fr.trav | (c->fr.twide ? TRAV_WIDE : 0)) {
         case TRAV_LANE | TRAV_WIDE: return f(Kind<TRAV_LANE | TRAV_WIDE>{});
         case TRAV_LANE: return f(Kind<TRAV_LANE>{});
         case TRAV_WIDE: return f(Kind<TRAV_LOCKSTEP | TRAV_WIDE>{});
@@ -1376,19 +1342,19 @@ static auto with_trav(const rs_context* c, Fn&& f) {
 template <class Fn>
 static auto with_flag(bool b, Fn&& f) { return b ? f(Kind<1>{}) : f(Kind<0>{}); }
 
+// the six pass times of a finished frame's events: gbuffer_initial, visibility, temporal, spatial, shade, total
+static void pass_times(const hipEvent_t* e, float v[6]) {
+    static const int k[6][2] = {{EV_BEGIN, EV_INIT}, {EV_INIT, EV_VIS}, {EV_VIS, EV_TEMPORAL},
+                                {EV_TEMPORAL, EV_SPATIAL}, {EV_SPATIAL, EV_SHADE}, {EV_BEGIN, EV_SHADE}};
+    for (int i = 0; i < 6; ++i) { v[i] = 0.0f; (void)hipEventElapsedTime(&v[i], e[k[i][0]], e[k[i][1]]); }
+}
 // fold a finished frame's pass times (event-ring slot s) into the running totals
 static void fold_slot(rs_context* c, int s) {
     if (!c->ev_pending[s]) return;
     c->ev_pending[s] = false;
-    hipEvent_t* e = c->evr[s];
-    if (hipEventSynchronize(e[EV_SHADE]) != hipSuccess) return;
-    float v[6] = {};
-    (void)hipEventElapsedTime(&v[0], e[EV_BEGIN], e[EV_INIT]);
-    (void)hipEventElapsedTime(&v[1], e[EV_INIT], e[EV_VIS]);
-    (void)hipEventElapsedTime(&v[2], e[EV_VIS], e[EV_TEMPORAL]);
-    (void)hipEventElapsedTime(&v[3], e[EV_TEMPORAL], e[EV_SPATIAL]);
-    (void)hipEventElapsedTime(&v[4], e[EV_SPATIAL], e[EV_SHADE]);
-    (void)hipEventElapsedTime(&v[5], e[EV_BEGIN], e[EV_SHADE]);
+    if (hipEventSynchronize(c->evr[s][EV_SHADE]) != hipSuccess) return;
+    float v[6];
+    pass_times(c->evr[s], v);
     for (int i = 0; i < 6; ++i) c->tot_ms[i] += v[i];
     c->tot_frames++;
 }
@@ -1398,28 +1364,29 @@ static void fold_slot(rs_context* c, int s) {
 // only, each tuning frame running alone: record_traversal_time).
 constexpr int kTuneRuns = 3;
 static void pick_traversal(rs_context* c, const rs_scene* s) {
-    c->tuning = false;
-    if (c->trav_mode == RS_TRAVERSAL_LOCKSTEP) { c->trav = TRAV_LOCKSTEP; return; }
-    if (c->trav_mode == RS_TRAVERSAL_LANE) { c->trav = TRAV_LANE; return; }
-    if (s->trav_choice >= 0) { c->trav = s->trav_choice; return; }
-    c->trav = s->trav_runs[TRAV_LOCKSTEP] <= s->trav_runs[TRAV_LANE] ? TRAV_LOCKSTEP : TRAV_LANE;
+    Frame& f = c->fr;
+    f.tuning = false;
+    if (c->sw.trav_mode == RS_TRAVERSAL_LOCKSTEP) { f.trav = TRAV_LOCKSTEP; return; }
+    if (c->sw.trav_mode == RS_TRAVERSAL_LANE) { f.trav = TRAV_LANE; return; }
+    if (s->trav_choice >= 0) { f.trav = s->trav_choice; return; }
+    f.trav = s->trav_runs[TRAV_LOCKSTEP] <= s->trav_runs[TRAV_LANE] ? TRAV_LOCKSTEP : TRAV_LANE;
     for (auto& e : c->tune_ev)
         if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; return; }   // untimed: stays un-tuned
-    c->tune_n = 0;
-    c->tuning = true;
+    f.tune_n = 0;
+    f.tuning = true;
     // full-frame tuning frames also record per-row cost for the tile-row dispatch order
-    c->tune_rows = false;
-    if (c->order_on && !c->track_rows && c->tile.y0 == 0 && c->tile.y1 == c->H) {
-        float*& p = c->d_tune_cost[c->trav];
+    f.tune_rows = false;
+    if (c->sw.order_on && !c->track_rows && f.tile.y0 == 0 && f.tile.y1 == c->H) {
+        float*& p = c->d_tune_cost[f.trav];
         if (!p && hipMalloc(&p, (size_t)c->H * sizeof(float)) == hipSuccess)
             (void)hipMemsetAsync(p, 0, (size_t)c->H * sizeof(float), c->stream);
-        c->tune_rows = p != nullptr;
+        f.tune_rows = p != nullptr;
     }
 }
 // The tuning frames' per-row wave time of the chosen kind -> tile-row dispatch order, costliest first
 // (ties: top row first).  Full frames only; the frames are already synchronised here.
 static void order_tile_rows(rs_context* c, int kind) {
-    c->tune_rows = false;
+    c->fr.tune_rows = false;
     if (!c->d_tune_cost[kind]) return;
     std::vector<float> rc((size_t)c->H);
     if (hipMemcpy(rc.data(), c->d_tune_cost[kind], rc.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return;
@@ -1434,95 +1401,98 @@ static void order_tile_rows(rs_context* c, int kind) {
     c->n_order = n;
 }
 static void record_traversal_time(rs_context* c) {
-    if (!c->tuning) return;
-    c->tuning = false;
-    // a tuning frame runs alone (rs_tile_begin: on the context's stream, and the next frame waits for
+    Frame& f = c->fr;
+    if (!f.tuning) return;
+    f.tuning = false;
+    // a tuning frame runs alone (bind_lane: on the context's stream, and the next frame waits for
     // it), and only its kernels are timed: begin..temporal, each spatial kernel, spatial..shade -- not
     // the halo exchanges of a multi-GPU frame, which wait for other ranks
     c->join_next = true;
     float ms = 0.0f, t = 0.0f;
-    if (hipEventSynchronize(c->ev[EV_SHADE]) != hipSuccess ||
-        hipEventElapsedTime(&ms, c->ev[EV_BEGIN], c->ev[EV_TEMPORAL]) != hipSuccess ||
-        hipEventElapsedTime(&t, c->ev[c->tune_n ? EV_SPATIAL : EV_TEMPORAL], c->ev[EV_SHADE]) != hipSuccess)
+    if (hipEventSynchronize(f.ev[EV_SHADE]) != hipSuccess ||
+        hipEventElapsedTime(&ms, f.ev[EV_BEGIN], f.ev[EV_TEMPORAL]) != hipSuccess ||
+        hipEventElapsedTime(&t, f.ev[f.tune_n ? EV_SPATIAL : EV_TEMPORAL], f.ev[EV_SHADE]) != hipSuccess)
         return;
     ms += t;
-    for (int i = 0; i + 1 < c->tune_n; i += 2) {
+    for (int i = 0; i + 1 < f.tune_n; i += 2) {
         if (hipEventElapsedTime(&t, c->tune_ev[i], c->tune_ev[i + 1]) != hipSuccess) return;
         ms += t;
     }
-    const rs_scene* s = c->scene;
-    if (++s->trav_runs[c->trav] > 1) s->trav_ms[c->trav] += ms;
+    const rs_scene* s = f.scene;
+    if (++s->trav_runs[f.trav] > 1) s->trav_ms[f.trav] += ms;
     if (s->trav_runs[TRAV_LOCKSTEP] >= kTuneRuns && s->trav_runs[TRAV_LANE] >= kTuneRuns) {
         s->trav_choice = s->trav_ms[TRAV_LANE] < s->trav_ms[TRAV_LOCKSTEP] ? TRAV_LANE : TRAV_LOCKSTEP;
         order_tile_rows(c, s->trav_choice);
     }
 }
-static size_t grid_waves(dim3 g, int waves_per_block = 4) { return (size_t)g.x * g.y * waves_per_block; }
 
-// the ray-count slot buffer k (of two: consecutive frames can be in flight) with >= need slots; the
+// lane L's ray-count slot buffer with >= need slots (one per lane: consecutive frames can be in flight); the
 // frame's launches then take consecutive slices of it (count_slot)
-static bool use_parts(rs_context* c, int k, size_t need) {
-    c->pk = k;
-    c->part_used = 0;
-    if (need > c->part_caps[k]) {
+static bool use_parts(rs_context* c, Lane& L, size_t need) {
+    L.part_used = 0;
+    if (need > L.part_cap) {
         sync_all(c);
-        if (c->parts[k]) hipFree(c->parts[k]);
-        c->parts[k] = nullptr; c->part_caps[k] = 0;
-        if (hipMalloc(&c->parts[k], need * sizeof(uint2)) != hipSuccess) { c->d_part = nullptr; c->part_cap = 0; return false; }
-        c->part_caps[k] = need;
+        if (L.part) hipFree(L.part);
+        L.part = nullptr; L.part_cap = 0;
+        if (hipMalloc(&L.part, need * sizeof(uint2)) != hipSuccess) { L.part = nullptr; return false; }
+        L.part_cap = need;
     }
-    c->d_part = c->parts[k]; c->part_cap = c->part_caps[k];
     return true;
 }
-// ray-count slots for one launch (rs_passes.h CountSlot); capacity is reserved in rs_tile_begin
-static CountSlot count_slot(rs_context* c, dim3 grid, int waves_per_block = 4) {
+// ray-count slots for one launch (rs_passes.h CountSlot); capacity is reserved when the frame begins
+static CountSlot count_slot(rs_context* c, Lane& L, dim3 grid, int waves_per_block = 4) {
     const size_t n = grid_waves(grid, waves_per_block);
-    if (c->part_used + n > c->part_cap) {       // more launches than reserved (a pass re-run): grow, keep slots
-        const size_t cap = 2 * (c->part_used + n);
+    if (L.part_used + n > L.part_cap) {         // more launches than reserved (a pass re-run): grow, keep slots
+        const size_t cap = 2 * (L.part_used + n);
         uint2* np = nullptr;
         sync_all(c);
         if (hipMalloc(&np, cap * sizeof(uint2)) == hipSuccess) {
-            if (c->part_used) hipMemcpy(np, c->d_part, c->part_used * sizeof(uint2), hipMemcpyDeviceToDevice);
-            hipFree(c->d_part);
-            c->d_part = c->parts[c->pk] = np; c->part_cap = c->part_caps[c->pk] = cap;
+            if (L.part_used) hipMemcpy(np, L.part, L.part_used * sizeof(uint2), hipMemcpyDeviceToDevice);
+            hipFree(L.part);
+            L.part = np; L.part_cap = cap;
         } else {
-            c->part_used = 0;                   // out of memory: recount from slot 0 (totals undercount)
+            L.part_used = 0;                    // out of memory: recount from slot 0 (totals undercount)
         }
     }
-    float* rows = c->track_rows ? c->d_rowcost : (c->tune_rows ? c->d_tune_cost[c->trav] : nullptr);
-    CountSlot s{c->d_part + c->part_used, &c->d_cnt->reproj_outside, rows, c->F.y0, c->F.y1};
-    c->part_used += n;
+    const Frame& f = c->fr;
+    float* rows = c->track_rows ? c->d_rowcost : (f.tune_rows ? c->d_tune_cost[f.trav] : nullptr);
+    CountSlot s{L.part + L.part_used, &L.cnt->reproj_outside, rows, f.F.y0, f.F.y1};
+    L.part_used += n;
     return s;
 }
-// reserve slots for every launch of a frame: initial + visibility + temporal + P spatial + shade
+// the frame's ray counts: lane L's slots -> its Counters and the running totals
+static hipError_t reduce_counts(rs_context* c, Lane& L, hipStream_t st) {
+    k_reduce_counts<<<kReduceBlocks, kReduceThreads, 0, st>>>(L.part, L.part_used, L.red, (unsigned*)(L.red + kReduceBlocks),
+                                                             L.cnt, c->d_tot);
+    return hipGetLastError();
+}
 // the wave-sorted initial pass (rs_passes.h k_gbuffer_initial_sorted) for the per-lane walks: sorting a
 // tile's shadow rays by octant x light bucket cuts C3's initial pass 16.27 -> 15.25 ms; the lockstep walk
 // already shares one node stream per wave and loses to the sort's extra phases (C2: 1.31 -> 1.69 ms)
 static bool want_sorted(const rs_context* c, const rs_frame_params* P, const rs_scene* s) {
-    if (P->m_area <= 0 || s->n_emis >= (1u << 21) || c->sort_mode == RS_SPLIT_OFF) return false;
-    return c->sort_mode == RS_SPLIT_ON || c->trav == TRAV_LANE;
+    if (P->m_area <= 0 || s->n_emis >= (1u << 21) || c->sw.sort_mode == RS_SPLIT_OFF) return false;
+    return c->sw.sort_mode == RS_SPLIT_ON || c->fr.trav == TRAV_LANE;
 }
 // the one-thread-per-pixel initial pass with the light tables in LDS (rs_passes.h LIGHT_LDS): when the scene's CDF
 // fits the kernel's static arrays and area candidates are drawn at all; larger scenes keep the global tables.
 // Lockstep walks only: the per-lane kernel is budgeted for 6 waves per SIMD, which 30 KB of LDS per workgroup
 // does not leave (and per-lane scenes take the sorted pass, whose LDS is full)
 static bool use_light_lds(const rs_context* c, const rs_frame_params* P, const rs_scene* s) {
-    return c->light_lds && c->trav == TRAV_LOCKSTEP && P->m_area > 0 && s->n_emis > 0 && s->n_emis <= (uint32_t)kLightLdsMax;
+    return c->sw.light_lds && c->fr.trav == TRAV_LOCKSTEP && P->m_area > 0 && s->n_emis > 0 && s->n_emis <= (uint32_t)kLightLdsMax;
 }
-static dim3 grid_split(int W, int ya, int yb) { return dim3((W + 7) / 8, (yb - ya + 7) / 8); }
 // the initial pass runs candidate-split when asked, or (AUTO) when one thread per pixel would give the
 // launch too few rounds of the device's resident waves (a rank's band of a multi-GPU frame) and
 // the walks are lockstep: per-lane walks are latency-bound and need the occupancy the split kernel's
 // LDS takes away (C3 1/8 band: 5.3 ms split vs 4.2 ms one thread per pixel)
 static bool want_split(const rs_context* c, const rs_frame_params* P, int gy0, int gy1) {
     if (P->m_area + P->m_brdf > kSplitMaxCand || P->m_brdf > kSplitMaxBrdf) return false;
-    if (c->split_mode == RS_SPLIT_ON) return true;
-    if (c->split_mode == RS_SPLIT_OFF) return false;
+    if (c->sw.split_mode == RS_SPLIT_ON) return true;
+    if (c->sw.split_mode == RS_SPLIT_OFF) return false;
     // with frames in flight the neighbouring frames fill a launch's tail: split only below one round
     // (C2 1/4 band, 1.4 rounds: 0.363 ms/frame unsplit vs 0.411 split with the cost-weighted groups, r04;
     // 1/8 band, 0.8 rounds: 0.209 split vs 0.26); one frame at a time, below 3 rounds (1/8 band 0.64 -> 0.40 ms)
     const size_t rounds = c->ahead > 0 ? 1 : 3;
-    return c->trav == TRAV_LOCKSTEP && grid_waves(grid_rows(c->W, gy0, gy1)) < rounds * c->wave_slots;
+    return c->fr.trav == TRAV_LOCKSTEP && grid_waves(grid_rows(c->W, gy0, gy1)) < rounds * c->wave_slots;
 }
 // the sorted initial pass by persistent waves (RESTIR_PERSIST_SORTED).  AUTO (default): with frames in flight
 // (run-ahead > 0) and more than one round of the one-launch kernel's waves, kPersistSortedWgs resident workgroups
@@ -1532,7 +1502,7 @@ static bool want_split(const rs_context* c, const rs_frame_params* P, int gy0, i
 // the one-launch kernel.
 constexpr int kPersistSortedWgs = 3;
 static int persist_sorted_wgs(rs_context* c) {
-    int& n = c->persist_sorted_wgs[c->trav | (c->twide ? TRAV_WIDE : 0)];
+    int& n = c->persist_sorted_wgs[c->fr.trav | (c->fr.twide ? TRAV_WIDE : 0)];
     if (!n) {
         const hipError_t e = with_trav(c, [&](auto T) {
             return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_gbuffer_initial_sorted_pq<T()>, 256, 0);
@@ -1547,45 +1517,39 @@ static int persist_sorted_grid_wgs(rs_context* c) {     // resident workgroups p
     return n;
 }
 static bool want_persist_sorted(rs_context* c, dim3 grid) {
-    if (c->persist_sorted == RS_SPLIT_OFF) return false;
-    if (c->persist_sorted == RS_SPLIT_ON) return true;
+    if (c->sw.persist_sorted == RS_SPLIT_OFF) return false;
+    if (c->sw.persist_sorted == RS_SPLIT_ON) return true;
     // full frames only, and not while row costs are being recorded: a throttled persistent launch charges its
     // early (costly, contended) tiles more and its late ones less than the one-launch kernel a band runs, so
     // bounds balanced on its row costs come out uneven (C4's eight 4K bands: max 9.59 vs 8.96 ms)
-    const bool full = c->tile.y0 == 0 && c->tile.y1 == c->H;
-    return c->ahead > 0 && full && !c->track_rows && !c->tune_rows &&
+    const bool full = c->fr.tile.y0 == 0 && c->fr.tile.y1 == c->H;
+    return c->ahead > 0 && full && !c->track_rows && !c->fr.tune_rows &&
            grid_waves(grid) > (size_t)c->cus * 4 * (size_t)persist_sorted_wgs(c);
 }
-// the sorted initial pass's hand-off buffers of lane k (FrameConst::cand_w, cand_ray: kSortChunk x 64 candidates per
+// the sorted initial pass's hand-off buffers of lane L (FrameConst::cand_w, cand_ray: kSortChunk x 64 candidates per
 // wave slot, 20 B each) for `slots` wave slots, grown on demand; false (nothing allocated) when the device is out of
 // memory.  Sized by the launch, not the frame: the persistent launch's resident waves (C3 1080p: 3 workgroups x 4
 // waves x 256 CUs x 20 KB = 63 MB per lane), a one-launch band its own tiles.
-static bool ensure_handoff(rs_context* c, int k, size_t slots) {
-    if (slots <= c->cand_slots[k]) return true;
+static bool ensure_handoff(rs_context* c, Lane& L, size_t slots) {
+    if (slots <= L.cand_slots) return true;
     sync_all(c);                                   // frames in flight on the lane may still read the old buffers
-    if (c->candw[k]) hipFree(c->candw[k]);
-    if (c->candr[k]) hipFree(c->candr[k]);
-    c->candw[k] = nullptr; c->candr[k] = nullptr; c->cand_slots[k] = 0;
+    if (L.candw) hipFree(L.candw);
+    if (L.candr) hipFree(L.candr);
+    L.candw = nullptr; L.candr = nullptr; L.cand_slots = 0;
     const size_t n = slots * (size_t)(kSortChunk * 64);
-    if (hipMalloc(&c->candw[k], n * sizeof(float)) != hipSuccess || hipMalloc(&c->candr[k], n * sizeof(float4)) != hipSuccess) {
+    if (hipMalloc(&L.candw, n * sizeof(float)) != hipSuccess || hipMalloc(&L.candr, n * sizeof(float4)) != hipSuccess) {
         (void)hipGetLastError();
-        if (c->candw[k]) hipFree(c->candw[k]);
-        c->candw[k] = nullptr; c->candr[k] = nullptr;
+        if (L.candw) hipFree(L.candw);
+        L.candw = nullptr; L.candr = nullptr;
         return false;
     }
-    c->cand_slots[k] = slots;
+    L.cand_slots = slots;
     return true;
 }
-static bool reserve_count_slots(rs_context* c, int k, const rs_frame_params* P, int gy0, int gy1, int y0, int y1,
-                                size_t extra = 0) {
-    const size_t spatial = grid_waves(grid_rows(c->W, y0, y1));
-    size_t need = (c->split ? grid_waves(grid_split(c->W, gy0, gy1), kSplit) : grid_waves(grid_rows(c->W, gy0, gy1))) +
-                  grid_waves(grid_rows(c->W, y0, y1)) * 4 + spatial * (size_t)std::max(0, P->spatial_passes) + extra;
-    return use_parts(c, k, need);
-}
 
-extern "C" int rs_tile_begin(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
-                             uint32_t frame_index, const rs_tile_desc* tile) {
+// ---- rs_tile_begin, step by step
+static int check_frame_args(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                            const rs_tile_desc* tile) {
     if (!c || !s || !cam || !P || !tile) return fail(c, RS_E_INVALID, "rs_tile_begin: null argument");
     if (s->ctx != c) return fail(c, RS_E_INVALID, "rs_tile_begin: scene belongs to another context");
     if (P->use_skybox && s->sky < 0)
@@ -1600,375 +1564,391 @@ extern "C" int rs_tile_begin(rs_context* c, const rs_scene* s, const rs_camera* 
     if (tile->y0 < 0 || tile->y1 > c->H || tile->y0 >= tile->y1 || tile->margin < 0 || tile->halo < 0 ||
         tile->halo > tile->margin)
         return fail(c, RS_E_INVALID, "rs_tile_begin: bad tile (need 0<=y0<y1<=H, 0<=halo<=margin)");
-    HIPCHK(c, enter(c));
-    c->scene = s; c->P = *P; c->tile = *tile; c->cam_last = *cam;
-    FrameConst& F = c->F;
-    F.m_area = P->m_area; F.m_brdf = P->m_brdf; F.k = P->spatial_neighbors; F.spatial_passes = P->spatial_passes;
-    F.cap = P->confidence_cap; F.radius = P->spatial_radius; F.min_normal_sim = P->min_normal_similarity;
-    F.max_depth_diff = P->max_depth_difference; F.do_spatial = P->do_spatial; F.do_temporal = P->do_temporal;
-    F.do_vis_pass = P->do_visibility_pass; F.reject = P->reject_dissimilar; F.mis = P->spatial_mis;
+    return RS_OK;
+}
+// what every render takes from its parameters (the ground-truth renders take nothing else)
+static FrameConst frame_const_base(const rs_context* c, const rs_frame_params* P, uint32_t frame_index, int y0, int y1,
+                                   int gy0, int gy1) {
+    FrameConst F = {};
     F.bg = vec3{P->bg_color[0], P->bg_color[1], P->bg_color[2]};
     F.tnear_off = P->tnear_offset; F.tfar_off = P->tfar_offset; F.normal_off = P->normal_offset;
     F.use_sky = P->use_skybox ? 1 : 0;
     F.seed = P->seed; F.frame = frame_index;
-    F.W = c->W; F.H = c->H;
-    F.y0 = tile->y0; F.y1 = tile->y1;
+    F.W = c->W; F.H = c->H; F.y0 = y0; F.y1 = y1; F.gy0 = gy0; F.gy1 = gy1;
+    return F;
+}
+// a ReSTIR frame's FrameConst; its camera goes into slot gnew of the G ring, the previous frame's comes from gcur
+static int fill_frame_const(rs_context* c, const rs_camera* cam, const rs_frame_params* P, uint32_t frame_index,
+                            const rs_tile_desc* tile, int gnew, FrameConst& F) {
+    F = frame_const_base(c, P, frame_index, tile->y0, tile->y1, std::max(0, tile->y0 - tile->margin),
+                         std::min(c->H, tile->y1 + tile->margin));
+    F.m_area = P->m_area; F.m_brdf = P->m_brdf; F.k = P->spatial_neighbors; F.spatial_passes = P->spatial_passes;
+    F.cap = P->confidence_cap; F.radius = P->spatial_radius; F.min_normal_sim = P->min_normal_similarity;
+    F.max_depth_diff = P->max_depth_difference; F.do_spatial = P->do_spatial; F.do_temporal = P->do_temporal;
+    F.do_vis_pass = P->do_visibility_pass; F.reject = P->reject_dissimilar; F.mis = P->spatial_mis;
     F.row_order = c->n_order ? c->d_order : nullptr; F.n_order = c->n_order;
     F.debug_reproj = P->debug_reprojection ? 1 : 0;
     if (F.debug_reproj && !c->d_dbg) HIPCHK(c, hipMalloc(&c->d_dbg, 2 * (size_t)c->W * c->H));
     F.dbg = c->d_dbg;
-    F.gy0 = std::max(0, tile->y0 - tile->margin); F.gy1 = std::min(c->H, tile->y1 + tile->margin);
-    // G-buffer ring (replaces gBufferLastFrame.setDataFrom, pg/simpleguidx11.cpp:480): this frame
-    // writes the slot after the current one; G[gcur] becomes the previous frame's
-    int gnew = (c->gcur + 1) % kGRing;
     make_camera(cam, c->H, c->gcam[gnew], F.inv_view);
     std::memcpy(c->ginv[gnew], F.inv_view, sizeof F.inv_view);
     std::memcpy(F.inv_view_prev, c->ginv[c->gcur], sizeof F.inv_view_prev);
     F.cam = c->gcam[gnew];
     F.camp = c->gcam[c->gcur];
-    // the frame's stream: lane seq mod (D+1) (run-ahead), else the context's stream
-    const int D = c->ahead;
-    c->li = D > 0 ? (int)(c->seq % (uint64_t)(D + 1)) : (c->fb_ring == 2 ? (int)(c->seq & 1) : 0);
-    // a frame that must follow work enqueued on the context's stream since the last frame (geometry
-    // updates, ...) simply runs on that stream (it is ordered after every earlier frame there); the next
-    // frame on its lane then waits for it
+    return RS_OK;
+}
+// The frame's lane (rs_frame_ring.h), traversal kind and stream: its lane's, or the context's -- a frame that must
+// follow work enqueued on the context's stream since the last frame (geometry updates, ...) simply runs on that
+// stream (it is ordered after every earlier frame there); the next frame on its lane then waits for it.
+static int bind_lane(rs_context* c, Frame& f, const rs_scene* s) {
+    f.li = ring::lane_of(c->seq, c->ahead, c->fb_ring);
+    Lane& L = c->lanes[f.li];
     pick_traversal(c, s);
-    c->twide = s->wide_on;
-    if (!c->fbs[c->li]) {                       // a lane's framebuffer, on first use: cleared on the context's
+    f.twide = s->wide_on;
+    if (!L.fb) {                                // a lane's framebuffer, on first use: cleared on the context's
         const size_t bytes = (size_t)c->W * c->H * 3 * sizeof(float);   // stream, so this frame runs there too
-        HIPCHK(c, hipMalloc(&c->fbs[c->li], bytes));
-        HIPCHK(c, hipMemsetAsync(c->fbs[c->li], 0, bytes, c->stream));
+        HIPCHK(c, hipMalloc(&L.fb, bytes));
+        HIPCHK(c, hipMemsetAsync(L.fb, 0, bytes, c->stream));
         c->join_next = true;
     }
-    const bool on_ctx = D == 0 || c->join_next || c->tuning;   // a traversal-tuning frame runs alone
-    c->fs = on_ctx ? c->stream : c->lane[c->li];
-    if (c->fb_read[c->li]) {                    // the lane's framebuffer is still being read back
-        HIPCHK(c, hipStreamWaitEvent(c->fs, c->fb_read[c->li], 0));
-        c->fb_read[c->li] = nullptr;
+    const bool on_ctx = c->ahead == 0 || c->join_next || f.tuning;   // a traversal-tuning frame runs alone
+    f.fs = on_ctx ? c->stream : L.stream;
+    if (L.fb_read) {                            // the lane's framebuffer is still being read back
+        HIPCHK(c, hipStreamWaitEvent(f.fs, L.fb_read, 0));
+        L.fb_read = nullptr;
     }
-    c->fb = c->fbs[c->li];
-    c->d_cnt = c->cnts[c->li]; c->d_red = c->reds[c->li];
-    // reservoir ring: `last` = the previous frame's final buffer (reservoirsLastFrame, a pointer swap,
-    // :477); this frame writes two buffers none of the D frames before it touches (they may still run)
-    c->last = c->r_last;
-    {
-        auto used = [&](int i) {
-            if (i == c->last) return true;
-            for (int g = 0; g < D; ++g)
-                if (i == c->rhist[g][0] || i == c->rhist[g][1] || i == c->rhist[g][2]) return true;
-            return false;
-        };
-        c->ra = 0;
-        while (used(c->ra)) ++c->ra;
-        c->rb = c->ra + 1;
-        while (used(c->rb)) ++c->rb;            // < kRRing: D frames touch <= 3D buffers, `last` among them
-        for (int g = kMaxAhead - 1; g > 0; --g)
-            for (int j = 0; j < 3; ++j) c->rhist[g][j] = c->rhist[g - 1][j];
-        c->rhist[0][0] = c->ra; c->rhist[0][1] = c->rb; c->rhist[0][2] = c->last;
-    }
-    c->rcur = c->ra;
-    const bool temporal = P->do_temporal && c->frames > 0;
-    const bool spatial = P->do_spatial && P->spatial_passes > 0;
-    c->shade_fused = !P->do_visibility_pass && !temporal && !spatial;
-    c->temporal_ran = c->spatial_ran = c->ev_temporal = false;
-    const DevScene S = s->dev();
+    return RS_OK;
+}
+// the reservoir buffers of the frame (rs_frame_ring.h pick_reservoirs) and the pass flags that follow from history
+static void pick_ring_buffers(rs_context* c, Frame& f) {
+    f.last = c->r_last;
+    ring::pick_reservoirs(f.last, c->ahead, c->rhist, f.ra, f.rb);
+    f.rcur = f.ra;
+    const bool temporal = f.P.do_temporal && c->frames > 0;
+    const bool spatial = f.P.do_spatial && f.P.spatial_passes > 0;
+    f.shade_fused = !f.P.do_visibility_pass && !temporal && !spatial;
+}
+// The initial pass's launch, chosen (and its hand-off buffers and the frame's count slots grown) before anything of
+// the frame is enqueued.  kind: 0 one thread per pixel (or candidate-split: fr.split), 1 wave-sorted (one launch), 2
+// wave-sorted by persistent waves.
+struct InitialPlan {
+    bool margins;
+    FrameConst Fi;                              // the rows of the initial pass's launch
+    int kind;
+    dim3 gg, gp;
+};
+static int plan_initial_pass(rs_context* c, Frame& f, Lane& L, InitialPlan& I) {
+    const FrameConst& F = f.F;
     // A band's G-buffer margin (the rows of the spatial halo beyond it) needs the G-buffer only.  Its rows get their
     // own small launch, so the initial pass's 8-row tiles start at the band's first row: otherwise the top and
     // bottom tile rows mix margin rows -- whose lanes idle through the whole candidate loop -- with band rows
     // (C2's 1/8 band: 145 G rows in 19 tile rows for 135 RIS rows, 11 % of the pass's waves idle).  Full frames
     // have no margin.
-    const bool margins = c->sep_margin && (F.gy0 < F.y0 || F.gy1 > F.y1);
-    FrameConst Fi = F;                          // the rows of the initial pass's launch
-    if (margins) { Fi.gy0 = F.y0; Fi.gy1 = F.y1; }
-    const size_t margin_waves = margins ? grid_waves(grid_rows(c->W, F.gy0, F.y0)) + grid_waves(grid_rows(c->W, F.y1, F.gy1)) : 0;
-    c->split = want_split(c, P, Fi.gy0, Fi.gy1);
-    // the initial pass's kernel, chosen (and its hand-off buffers grown) before anything of the frame is enqueued:
-    // 0 one thread per pixel, 1 wave-sorted (one launch), 2 wave-sorted by persistent waves
-    const dim3 gg = grid_rows(c->W, Fi.gy0, Fi.gy1), gb = grid_rows(c->W, F.y0, F.y1);
-    int init_kind = 0;
-    dim3 gp(1);
-    if (!c->split && want_sorted(c, P, s)) {
-        init_kind = want_persist_sorted(c, gg) ? 2 : 1;
-        if (init_kind == 2)
-            gp = dim3((unsigned)std::min<size_t>((size_t)gg.x * gg.y, (size_t)c->cus * (size_t)persist_sorted_grid_wgs(c)));
+    I.margins = c->sw.sep_margin && (F.gy0 < F.y0 || F.gy1 > F.y1);
+    I.Fi = F;
+    if (I.margins) { I.Fi.gy0 = F.y0; I.Fi.gy1 = F.y1; }
+    const size_t margin_waves = I.margins ? grid_waves(grid_rows(c->W, F.gy0, F.y0)) + grid_waves(grid_rows(c->W, F.y1, F.gy1)) : 0;
+    f.split = want_split(c, &f.P, I.Fi.gy0, I.Fi.gy1);
+    I.gg = grid_rows(c->W, I.Fi.gy0, I.Fi.gy1);
+    I.kind = 0;
+    I.gp = dim3(1);
+    if (!f.split && want_sorted(c, &f.P, f.scene)) {
+        I.kind = want_persist_sorted(c, I.gg) ? 2 : 1;
+        if (I.kind == 2)
+            I.gp = dim3((unsigned)std::min<size_t>((size_t)I.gg.x * I.gg.y, (size_t)c->cus * (size_t)persist_sorted_grid_wgs(c)));
         // one slot per resident wave of the persistent launch (reused tile after tile), else per 8x8 tile of the launch
-        const size_t slots = init_kind == 2 ? (size_t)gp.x * 4 : (size_t)gg.x * gg.y * 4;
-        if (!ensure_handoff(c, c->li, slots)) init_kind = 0;   // out of memory: the one-thread-per-pixel pass (same bits)
+        const size_t slots = I.kind == 2 ? (size_t)I.gp.x * 4 : (size_t)I.gg.x * I.gg.y * 4;
+        if (!ensure_handoff(c, L, slots)) I.kind = 0;   // out of memory: the one-thread-per-pixel pass (same bits)
     }
-    if (!reserve_count_slots(c, c->li, P, Fi.gy0, Fi.gy1, F.y0, F.y1, margin_waves))
-        return fail(c, RS_E_HIP, "hipMalloc(count slots) failed");
-    if (c->fs != c->stream && c->lane_wait[c->li]) {   // this lane's previous frame ran on the context's stream
-        HIPCHK(c, hipStreamWaitEvent(c->fs, c->lane_wait[c->li], 0));
-    }
-    c->lane_wait[c->li] = nullptr;
-    // frames start in order (the previous frame has started -- so every frame up to f-D-1 has finished:
-    // the one on this lane by stream order, earlier ones by induction): frames f-D..f-1 are the only
-    // ones that can still run beside this frame
-    if (c->fs != c->stream && c->prev_begin) HIPCHK(c, hipStreamWaitEvent(c->fs, c->prev_begin, 0));
-    if (s->update_recorded) HIPCHK(c, hipStreamWaitEvent(c->fs, s->update_ev, 0));   // the scene copy it reads
-    c->frame_scene = s; c->frame_gen = s->gen;
-    c->geo_prev = c->geo_last; c->geo_prev_scene = c->geo_last_scene; c->prevgeo_read = false;
+    const size_t need = ring::count_slot_need(c->W, I.Fi.gy0, I.Fi.gy1, F.y0, F.y1, f.split ? kSplit : 0, f.P.spatial_passes,
+                                              margin_waves);
+    if (!use_parts(c, L, need)) return fail(c, RS_E_HIP, "hipMalloc(count slots) failed");
+    return RS_OK;
+}
+// What the frame's stream waits for, its event slot and its start.  Frames start in order (the previous frame has
+// started -- so every frame up to f-D-1 has finished: the one on this lane by stream order, earlier ones by
+// induction): frames f-D..f-1 are the only ones that can still run beside this frame.
+static int order_frame(rs_context* c, Frame& f, Lane& L, const rs_scene* s) {
+    if (f.fs != c->stream && L.wait) HIPCHK(c, hipStreamWaitEvent(f.fs, L.wait, 0));   // the lane's previous frame ran
+    L.wait = nullptr;                                                                  // on the context's stream
+    if (f.fs != c->stream && c->prev_begin) HIPCHK(c, hipStreamWaitEvent(f.fs, c->prev_begin, 0));
+    if (s->update_recorded) HIPCHK(c, hipStreamWaitEvent(f.fs, s->update_ev, 0));   // the scene copy it reads
+    f.frame_gen = s->gen;
+    f.geo_prev = c->geo_last; f.geo_prev_scene = c->geo_last_scene;
     c->join_next = false;
     // (the frame's Counters need no memset: k_reduce_counts stores rays/primary, and the initial pass
     // zeroes reproj_outside before the temporal pass can count -- one API call less per frame)
-    c->slot = (int)(c->seq++ % rs_context::kEvRing);
-    fold_slot(c, c->slot);                      // the slot's previous frame (kEvRing frames ago)
-    for (int i = 0; i < EV_COUNT; ++i) c->ev[i] = c->evr[c->slot][i];
-    HIPCHK(c, hipEventRecord(c->ev[EV_BEGIN], c->fs));
-    c->prev_begin = c->ev[EV_BEGIN];
-    if (margins) {                              // the margin rows' G-buffer (no RIS rows: the candidate loops exit)
-        const int rr[2][2] = {{F.gy0, F.y0}, {F.y1, F.gy1}};
-        for (const auto& r : rr) {
-            if (r[0] >= r[1]) continue;
-            FrameConst Fm = F;
-            Fm.gy0 = r[0]; Fm.gy1 = r[1];
-            const dim3 gm = grid_rows(c->W, r[0], r[1]);
-            with_trav(c, [&](auto T) {
-                k_gbuffer_initial<T()><<<gm, 256, 0, c->fs>>>(S, Fm, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, 0, count_slot(c, gm));
-            });
-            HIPCHK(c, hipGetLastError());
-        }
-    }
-    if (c->split) {
-        const dim3 gs = grid_split(c->W, Fi.gy0, Fi.gy1);
+    f.slot = (int)(c->seq++ % rs_context::kEvRing);
+    fold_slot(c, f.slot);                       // the slot's previous frame (kEvRing frames ago)
+    f.ev = c->evr[f.slot];
+    HIPCHK(c, hipEventRecord(f.ev[EV_BEGIN], f.fs));
+    c->prev_begin = f.ev[EV_BEGIN];
+    return RS_OK;
+}
+// the margin rows' G-buffer (no RIS rows: the candidate loops exit)
+static int launch_margin_rows(rs_context* c, Frame& f, Lane& L, const DevScene& S, int gnew) {
+    const FrameConst& F = f.F;
+    const int rr[2][2] = {{F.gy0, F.y0}, {F.y1, F.gy1}};
+    for (const auto& r : rr) {
+        if (r[0] >= r[1]) continue;
+        FrameConst Fm = F;
+        Fm.gy0 = r[0]; Fm.gy1 = r[1];
+        const dim3 gm = grid_rows(c->W, r[0], r[1]);
         with_trav(c, [&](auto T) {
-            k_gbuffer_initial_split<T()><<<gs, 64 * kSplit, split_lds_bytes(P->m_area + P->m_brdf, P->m_brdf), c->fs>>>(
-                S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, c->shade_fused ? 1 : 0, count_slot(c, gs, kSplit));
-        });
-    } else if (init_kind > 0) {
-        Fi.cand_w = c->candw[c->li];
-        Fi.cand_ray = c->candr[c->li];
-        if (init_kind == 2) {
-            // persistent waves, each pulling 8x8 tiles (rs_passes.h k_gbuffer_initial_sorted_pq); the queue's counters
-            // from zero on the frame's stream (the last exiting wave also re-arms them, but an aborted launch would
-            // leave every later one pulling past the end)
-            const uint32_t nt = gg.x * gg.y * 4u;
-            HIPCHK(c, hipMemsetAsync(c->qctr[c->li], 0, 4 * sizeof(uint32_t), c->fs));
-            with_trav(c, [&](auto T) {
-                k_gbuffer_initial_sorted_pq<T()><<<gp, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb,
-                                                                         c->shade_fused ? 1 : 0, count_slot(c, gp),
-                                                                         TileQ{c->qctr[c->li], nt});
-            });
-        } else {
-            with_trav(c, [&](auto T) {
-                k_gbuffer_initial_sorted<T()><<<gg, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb,
-                                                                      c->shade_fused ? 1 : 0, count_slot(c, gg));
-            });
-        }
-    } else {
-        const bool lds = use_light_lds(c, P, s);          // lockstep kinds only: LIGHT_LDS exists for those two
-        with_trav(c, [&](auto T) {
-            const CountSlot cs = count_slot(c, gg);
-            const int fuse = c->shade_fused ? 1 : 0;
-            if constexpr (!trav_lane(T())) {
-                if (lds) {
-                    k_gbuffer_initial<T() | LIGHT_LDS><<<gg, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, fuse, cs);
-                    return;
-                }
-            }
-            k_gbuffer_initial<T()><<<gg, 256, 0, c->fs>>>(S, Fi, c->G[gnew], ResBuf{c->R[c->ra]}, c->fb, fuse, cs);
-        });
-    }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[EV_INIT], c->fs));
-    if (P->do_visibility_pass) {
-        with_trav(c, [&](auto T) {
-            k_visibility<T()><<<gb, 256, 0, c->fs>>>(S, F, c->G[gnew], ResBuf{c->R[c->ra]}, count_slot(c, gb));
+            k_gbuffer_initial<T()><<<gm, 256, 0, f.fs>>>(S, Fm, c->G[gnew], ResBuf{c->R[f.ra]}, L.fb, 0, count_slot(c, L, gm));
         });
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipEventRecord(c->ev[EV_VIS], c->fs));
+    return RS_OK;
+}
+static int launch_initial_pass(rs_context* c, Frame& f, Lane& L, const DevScene& S, int gnew, InitialPlan& I) {
+    const rs_frame_params* P = &f.P;
+    const GBuf& G = c->G[gnew];
+    const ResBuf R{c->R[f.ra]};
+    const int fuse = f.shade_fused ? 1 : 0;
+    if (f.split) {
+        const dim3 gs = grid_split(c->W, I.Fi.gy0, I.Fi.gy1);
+        with_trav(c, [&](auto T) {
+            k_gbuffer_initial_split<T()><<<gs, 64 * kSplit, split_lds_bytes(P->m_area + P->m_brdf, P->m_brdf), f.fs>>>(
+                S, I.Fi, G, R, L.fb, fuse, count_slot(c, L, gs, kSplit));
+        });
+    } else if (I.kind > 0) {
+        I.Fi.cand_w = L.candw;
+        I.Fi.cand_ray = L.candr;
+        if (I.kind == 2) {
+            // persistent waves, each pulling 8x8 tiles (rs_passes.h k_gbuffer_initial_sorted_pq); the queue's counters
+            // from zero on the frame's stream (the last exiting wave also re-arms them, but an aborted launch would
+            // leave every later one pulling past the end)
+            const uint32_t nt = I.gg.x * I.gg.y * 4u;
+            HIPCHK(c, hipMemsetAsync(L.qctr, 0, 4 * sizeof(uint32_t), f.fs));
+            with_trav(c, [&](auto T) {
+                k_gbuffer_initial_sorted_pq<T()><<<I.gp, 256, 0, f.fs>>>(S, I.Fi, G, R, L.fb, fuse, count_slot(c, L, I.gp),
+                                                                          TileQ{L.qctr, nt});
+            });
+        } else {
+            with_trav(c, [&](auto T) {
+                k_gbuffer_initial_sorted<T()><<<I.gg, 256, 0, f.fs>>>(S, I.Fi, G, R, L.fb, fuse, count_slot(c, L, I.gg));
+            });
+        }
+    } else {
+        const bool lds = use_light_lds(c, P, f.scene);    // lockstep kinds only: LIGHT_LDS exists for those two
+        with_trav(c, [&](auto T) {
+            const CountSlot cs = count_slot(c, L, I.gg);
+            if constexpr (!trav_lane(T())) {
+                if (lds) {
+                    k_gbuffer_initial<T() | LIGHT_LDS><<<I.gg, 256, 0, f.fs>>>(S, I.Fi, G, R, L.fb, fuse, cs);
+                    return;
+                }
+            }
+            k_gbuffer_initial<T()><<<I.gg, 256, 0, f.fs>>>(S, I.Fi, G, R, L.fb, fuse, cs);
+        });
+    }
+    HIPCHK(c, hipGetLastError());
+    return RS_OK;
+}
+
+extern "C" int rs_tile_begin(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                             uint32_t frame_index, const rs_tile_desc* tile) {
+    if (int rc = check_frame_args(c, s, cam, P, tile)) return rc;
+    HIPCHK(c, enter(c));
+    Frame& f = c->fr;
+    f = Frame{};                                // nothing of the previous frame survives
+    f.scene = s; f.P = *P; f.tile = *tile; c->cam_last = *cam;
+    const int gnew = ring::g_next(c->gcur);
+    if (int rc = fill_frame_const(c, cam, P, frame_index, tile, gnew, f.F)) return rc;
+    if (int rc = bind_lane(c, f, s)) return rc;
+    Lane& L = c->lanes[f.li];
+    pick_ring_buffers(c, f);
+    InitialPlan I;
+    if (int rc = plan_initial_pass(c, f, L, I)) return rc;
+    if (int rc = order_frame(c, f, L, s)) return rc;
+    const DevScene S = s->dev();
+    if (I.margins)
+        if (int rc = launch_margin_rows(c, f, L, S, gnew)) return rc;
+    if (int rc = launch_initial_pass(c, f, L, S, gnew, I)) return rc;
+    HIPCHK(c, hipEventRecord(f.ev[EV_INIT], f.fs));
+    if (P->do_visibility_pass) {
+        const dim3 gb = grid_rows(c->W, f.F.y0, f.F.y1);
+        with_trav(c, [&](auto T) {
+            k_visibility<T()><<<gb, 256, 0, f.fs>>>(S, f.F, c->G[gnew], ResBuf{c->R[f.ra]}, count_slot(c, L, gb));
+        });
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipEventRecord(f.ev[EV_VIS], f.fs));
     c->gprev = c->gcur;
     c->gcur = gnew;       // G[gcur] = this frame, G[gprev] = previous frame
-    c->prev_done = c->last_done;
-    c->active = true;
+    f.prev_done = c->last_done;
+    f.active = true;
     return RS_OK;
 }
 
 extern "C" int rs_tile_stream(rs_context* c, void** stream, int* lane) {
     if (!c || !stream) return fail(c, RS_E_INVALID, "rs_tile_stream: null argument");
-    if (!c->active) return fail(c, RS_E_INVALID, "rs_tile_stream: no frame in flight");
-    *stream = (void*)c->fs;
-    if (lane) *lane = c->li;
+    if (!c->fr.active) return fail(c, RS_E_INVALID, "rs_tile_stream: no frame in flight");
+    *stream = (void*)c->fr.fs;
+    if (lane) *lane = c->fr.li;
     return RS_OK;
 }
 
 extern "C" int rs_tile_halo_ptr(rs_context* c, int which, void** dptr, size_t* bytes) {
-    if (!c || !dptr || !bytes || !c->active) return fail(c, RS_E_INVALID, "rs_tile_halo_ptr: no frame in flight");
-    const int h = c->tile.halo, W = c->W;
-    int r0;
-    switch (which) {
-        case 0: r0 = c->tile.y0 - h; break;
-        case 1: r0 = c->tile.y1; break;
-        case 2: r0 = c->tile.y0; break;
-        case 3: r0 = c->tile.y1 - h; break;
-        default: return fail(c, RS_E_INVALID, "rs_tile_halo_ptr: which must be 0..3");
-    }
+    if (!c || !dptr || !bytes || !c->fr.active) return fail(c, RS_E_INVALID, "rs_tile_halo_ptr: no frame in flight");
+    const rs_tile_desc& tile = c->fr.tile;
+    const int h = tile.halo, W = c->W;
+    if (which < 0 || which > 3) return fail(c, RS_E_INVALID, "rs_tile_halo_ptr: which must be 0..3");
+    const int rows[4] = {tile.y0 - h, tile.y1, tile.y0, tile.y1 - h}, r0 = rows[which];
     if (h == 0 || r0 < 0 || r0 + h > c->H) { *dptr = nullptr; *bytes = 0; return RS_OK; }
-    *dptr = (void*)(c->R[c->rcur] + 3 * (size_t)r0 * W);
+    *dptr = (void*)(c->R[c->fr.rcur] + 3 * (size_t)r0 * W);
     *bytes = (size_t)h * W * 3 * sizeof(float4);
     return RS_OK;
 }
 
-extern "C" int rs_tile_temporal(rs_context* c) {
-    if (!c || !c->active) return fail(c, RS_E_INVALID, "rs_tile_temporal: no frame in flight");
-    HIPCHK(c, enter(c));
-    if (c->P.do_temporal && c->frames > 0 && !c->temporal_ran) {
-        const DevScene S = c->scene->dev();
-        const dim3 gb = grid_rows(c->W, c->F.y0, c->F.y1);
+// The temporal pass if the frame has one and it has not run, then EV_TEMPORAL, once per frame: the tile calls after
+// rs_tile_begin all start here, so a caller may skip rs_tile_temporal.
+static int ensure_temporal(rs_context* c) {
+    Frame& f = c->fr;
+    if (f.P.do_temporal && c->frames > 0 && !f.temporal_ran) {
+        const DevScene S = f.scene->dev();
+        const dim3 gb = grid_rows(c->W, f.F.y0, f.F.y1);
         // the previous frame's final reservoirs and G-buffer (another lane may still be finishing it)
-        if (c->prev_done && c->fs != c->stream) HIPCHK(c, hipStreamWaitEvent(c->fs, c->prev_done, 0));
+        if (f.prev_done && f.fs != c->stream) HIPCHK(c, hipStreamWaitEvent(f.fs, f.prev_done, 0));
         const size_t npx = (size_t)c->W * c->H;
         // a tile rebuilds previous-frame G elements beyond its rows with the previous frame's geometry
         DevScene Sp = S;
-        const bool partial = c->F.gy0 > 0 || c->F.gy1 < c->H;
-        const bool twide = c->twide;
-        if (partial && c->geo_prev_scene == c->scene && c->geo_prev != c->scene->geo_gen) {
-            if (c->scene->dev_of(c->geo_prev, Sp)) c->prevgeo_read = true;
-            else { Sp = S; c->prevgeo_missing++; }     // two updates between frames: the a_* copy moved on
+        const bool partial = f.F.gy0 > 0 || f.F.gy1 < c->H;
+        const bool twide = f.twide;
+        if (partial && f.geo_prev_scene == f.scene && f.geo_prev != f.scene->geo_gen) {
+            if (f.scene->dev_of(f.geo_prev, Sp)) f.prevgeo_read = true;
+            else { Sp = S; c->prevgeo_missing++; }     // two updates between frames: the alt copy moved on
         }
         // the kernel walks S and Sp with one traversal kind: when either lacks its 8-wide tree (a generation
         // held without one), this launch walks both binary trees (same hits, rs_scene.h)
-        if (!S.wnodes || !Sp.wnodes) c->twide = false;
-        if (c->F.debug_reproj) HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, 2 * npx, c->fs));
-        c->F.canon_vis = c->P.do_visibility_pass ? 0 : 1;   // the current reservoir's sample: tested from this pixel
+        if (!S.wnodes || !Sp.wnodes) f.twide = false;
+        if (f.F.debug_reproj) HIPCHK(c, hipMemsetAsync(c->d_dbg, 0, 2 * npx, f.fs));
+        f.F.canon_vis = f.P.do_visibility_pass ? 0 : 1;   // the current reservoir's sample: tested from this pixel
         // the wave-sorted shadow rays (TEMPORAL_SORT) unless RESTIR_SORT_TEMPORAL=off: C3 (per-lane) temporal
         // 1.54 -> 1.36 ms, C5 (lockstep) 0.210 -> 0.191 ms
-        const bool tsort = c->sort_temporal != RS_SPLIT_OFF;
+        const bool tsort = c->sw.sort_temporal != RS_SPLIT_OFF;
         with_flag(partial, [&](auto Band) { with_flag(tsort, [&](auto Sort) { with_trav(c, [&](auto T) {
-            k_temporal<T() | (Band() ? TEMPORAL_BAND : 0) | (Sort() ? TEMPORAL_SORT : 0)><<<gb, 256, 0, c->fs>>>(
-                S, Sp, c->F, c->G[c->gcur], c->G[c->gprev], ResBuf{c->R[c->rcur]}, ResBuf{c->R[c->last]}, ResBuf{c->R[c->rb]},
-                count_slot(c, gb));
+            k_temporal<T() | (Band() ? TEMPORAL_BAND : 0) | (Sort() ? TEMPORAL_SORT : 0)><<<gb, 256, 0, f.fs>>>(
+                S, Sp, f.F, c->G[c->gcur], c->G[c->gprev], ResBuf{c->R[f.rcur]}, ResBuf{c->R[f.last]}, ResBuf{c->R[f.rb]},
+                count_slot(c, c->lane(), gb));
         }); }); });
-        c->twide = twide;
+        f.twide = twide;
         HIPCHK(c, hipGetLastError());
-        if (c->F.debug_reproj) {
-            k_debug_reproj<<<(unsigned)((npx + 255) / 256), 256, 0, c->fs>>>(c->G[c->gcur], c->d_dbg, (uint32_t)npx);
+        if (f.F.debug_reproj) {
+            k_debug_reproj<<<(unsigned)((npx + 255) / 256), 256, 0, f.fs>>>(c->G[c->gcur], c->d_dbg, (uint32_t)npx);
             HIPCHK(c, hipGetLastError());
         }
-        c->rcur = c->rb;
-        c->temporal_ran = true;
+        f.rcur = f.rb;
+        f.temporal_ran = true;
     }
-    if (!c->ev_temporal) {
-        HIPCHK(c, hipEventRecord(c->ev[EV_TEMPORAL], c->fs));
-        c->ev_temporal = true;
+    if (!f.ev_temporal) {
+        HIPCHK(c, hipEventRecord(f.ev[EV_TEMPORAL], f.fs));
+        f.ev_temporal = true;
     }
     return RS_OK;
 }
+extern "C" int rs_tile_temporal(rs_context* c) {
+    if (!c || !c->fr.active) return fail(c, RS_E_INVALID, "rs_tile_temporal: no frame in flight");
+    HIPCHK(c, enter(c));
+    return ensure_temporal(c);
+}
 
 extern "C" int rs_tile_spatial(rs_context* c, int pass_index) {
-    if (!c || !c->active) return fail(c, RS_E_INVALID, "rs_tile_spatial: no frame in flight");
-    if (!(c->P.do_spatial && pass_index >= 0 && pass_index < c->P.spatial_passes)) return RS_OK;
+    if (!c || !c->fr.active) return fail(c, RS_E_INVALID, "rs_tile_spatial: no frame in flight");
+    Frame& f = c->fr;
+    if (!(f.P.do_spatial && pass_index >= 0 && pass_index < f.P.spatial_passes)) return RS_OK;
     HIPCHK(c, enter(c));
-    if (c->P.do_temporal && c->frames > 0 && !c->temporal_ran) {
-        int rc = rs_tile_temporal(c);
-        if (rc) return rc;
-    }
-    if (!c->ev_temporal) {
-        HIPCHK(c, hipEventRecord(c->ev[EV_TEMPORAL], c->fs));
-        c->ev_temporal = true;
-    }
-    const DevScene S = c->scene->dev();
-    int dst = (c->rcur == c->ra) ? c->rb : c->ra;
-    int fuse = (pass_index == c->P.spatial_passes - 1) ? 1 : 0;
+    if (int rc = ensure_temporal(c)) return rc;
+    Lane& L = c->lanes[f.li];
+    const DevScene S = f.scene->dev();
+    int dst = (f.rcur == f.ra) ? f.rb : f.ra;
+    int fuse = (pass_index == f.P.spatial_passes - 1) ? 1 : 0;
     // the canonical reservoir's sample was visibility-tested from this very pixel (same origin, target, tnear and
     // tfar: the same ray) when it was selected -- by the initial pass, the temporal pass (p-hat at the current
     // surface) or the previous spatial pass -- except after a visibility pass, which keeps occluded samples with
     // W = 0 (pg/ReSTIRIntegrator.cpp:302-312); the temporal pass passes such a reservoir through on a failed
     // reprojection, so with the visibility pass only passes >= 1 know it
-    c->F.canon_vis = (!c->P.do_visibility_pass || pass_index > 0) ? 1 : 0;
-    const dim3 gb = grid_rows(c->W, c->F.y0, c->F.y1);
+    f.F.canon_vis = (!f.P.do_visibility_pass || pass_index > 0) ? 1 : 0;
+    const dim3 gb = grid_rows(c->W, f.F.y0, f.F.y1);
     {
-        const CountSlot cs = count_slot(c, gb);
+        const CountSlot cs = count_slot(c, L, gb);
         const GBuf& G = c->G[c->gcur];
-        const ResBuf Rr{c->R[c->rcur]}, Rw{c->R[dst]};
-        const bool cm = c->F.mis == MIS_CONSTANT;
-        const bool tev = c->tuning && c->tune_n + 2 <= (int)(sizeof(c->tune_ev) / sizeof(c->tune_ev[0]));
-        if (tev) HIPCHK(c, hipEventRecord(c->tune_ev[c->tune_n], c->fs));
-        const bool ssort = c->sort_spatial == RS_SPLIT_ON || (c->sort_spatial == RS_SPLIT_AUTO && c->trav == TRAV_LANE);
-        if (ssort && cm && c->F.k + 1 <= kSpatialSortMax) {
+        const ResBuf Rr{c->R[f.rcur]}, Rw{c->R[dst]};
+        const bool cm = f.F.mis == MIS_CONSTANT;
+        const bool tev = f.tuning && f.tune_n + 2 <= (int)(sizeof(c->tune_ev) / sizeof(c->tune_ev[0]));
+        if (tev) HIPCHK(c, hipEventRecord(c->tune_ev[f.tune_n], f.fs));
+        const bool ssort = c->sw.sort_spatial == RS_SPLIT_ON || (c->sw.sort_spatial == RS_SPLIT_AUTO && f.trav == TRAV_LANE);
+        if (ssort && cm && f.F.k + 1 <= kSpatialSortMax) {
             with_trav(c, [&](auto T) {
-                k_spatial_sorted<T()><<<gb, 256, 0, c->fs>>>(S, c->F, G, Rr, Rw, pass_index, fuse, c->fb, cs);
+                k_spatial_sorted<T()><<<gb, 256, 0, f.fs>>>(S, f.F, G, Rr, Rw, pass_index, fuse, L.fb, cs);
             });
         } else {
             // a small lockstep launch takes the RS_SPATIAL_WAVES_SMALL budget (the per-lane kinds have one budget)
             const bool small = grid_waves(gb) < (size_t)2 * c->wave_slots;
             with_flag(small, [&](auto Small) { with_trav(c, [&](auto T) { with_flag(cm, [&](auto CM) {
                 constexpr int SM = trav_lane(T()) ? 0 : Small();
-                k_spatial<T(), CM(), SM><<<gb, 256, 0, c->fs>>>(S, c->F, G, Rr, Rw, pass_index, fuse, c->fb, cs);
+                k_spatial<T(), CM(), SM><<<gb, 256, 0, f.fs>>>(S, f.F, G, Rr, Rw, pass_index, fuse, L.fb, cs);
             }); }); });
         }
         if (tev) {
-            HIPCHK(c, hipEventRecord(c->tune_ev[c->tune_n + 1], c->fs));
-            c->tune_n += 2;
+            HIPCHK(c, hipEventRecord(c->tune_ev[f.tune_n + 1], f.fs));
+            f.tune_n += 2;
         }
     }
     HIPCHK(c, hipGetLastError());
-    c->rcur = dst;
-    if (fuse) c->shade_fused = true;
-    c->spatial_ran = true;
-    HIPCHK(c, hipEventRecord(c->ev[EV_SPATIAL], c->fs));
+    f.rcur = dst;
+    if (fuse) f.shade_fused = true;
+    f.spatial_ran = true;
+    HIPCHK(c, hipEventRecord(f.ev[EV_SPATIAL], f.fs));
     return RS_OK;
 }
 
 extern "C" int rs_tile_finish(rs_context* c, const float** band_rgb, rs_pass_times* t) {
-    if (!c || !c->active) return fail(c, RS_E_INVALID, "rs_tile_finish: no frame in flight");
+    if (!c || !c->fr.active) return fail(c, RS_E_INVALID, "rs_tile_finish: no frame in flight");
     HIPCHK(c, enter(c));
-    if (c->P.do_temporal && c->frames > 0 && !c->temporal_ran) {
-        int rc = rs_tile_temporal(c);
-        if (rc) return rc;
-    }
-    if (!c->ev_temporal) {
-        HIPCHK(c, hipEventRecord(c->ev[EV_TEMPORAL], c->fs));
-        c->ev_temporal = true;
-    }
-    if (!c->spatial_ran) HIPCHK(c, hipEventRecord(c->ev[EV_SPATIAL], c->fs));
-    if (!c->shade_fused) {
-        const DevScene S = c->scene->dev();
-        const dim3 gb = grid_rows(c->W, c->F.y0, c->F.y1);
+    if (int rc = ensure_temporal(c)) return rc;
+    Frame& f = c->fr;
+    Lane& L = c->lanes[f.li];
+    if (!f.spatial_ran) HIPCHK(c, hipEventRecord(f.ev[EV_SPATIAL], f.fs));
+    if (!f.shade_fused) {
+        const DevScene S = f.scene->dev();
+        const dim3 gb = grid_rows(c->W, f.F.y0, f.F.y1);
         with_trav(c, [&](auto T) {
-            k_shade<T()><<<gb, 256, 0, c->fs>>>(S, c->F, c->G[c->gcur], ResBuf{c->R[c->rcur]}, c->fb, count_slot(c, gb));
+            k_shade<T()><<<gb, 256, 0, f.fs>>>(S, f.F, c->G[c->gcur], ResBuf{c->R[f.rcur]}, L.fb, count_slot(c, L, gb));
         });
         HIPCHK(c, hipGetLastError());
     }
-    HIPCHK(c, hipEventRecord(c->ev[EV_SHADE], c->fs));
-    c->ev_pending[c->slot] = true;
-    k_reduce_counts<<<kReduceBlocks, kReduceThreads, 0, c->fs>>>(c->d_part, c->part_used, c->d_red,
-                                                                 (unsigned*)(c->d_red + kReduceBlocks), c->d_cnt, c->d_tot);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[EV_DONE], c->fs));
-    c->last_done = c->ev[EV_DONE];
-    c->lane_scene[c->li] = c->frame_scene; c->lane_gen[c->li] = c->frame_gen; c->lane_done[c->li] = c->ev[EV_DONE];
-    c->lane_prevgeo[c->li] = c->prevgeo_read;
-    c->geo_last = c->frame_scene ? c->frame_scene->geo_gen : 0; c->geo_last_scene = c->frame_scene;
-    if (c->fs == c->stream && c->ahead > 0) c->lane_wait[c->li] = c->ev[EV_DONE];
-    if (c->fs != c->stream) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev[EV_DONE], 0));   // sequential semantics
+    HIPCHK(c, hipEventRecord(f.ev[EV_SHADE], f.fs));
+    c->ev_pending[f.slot] = true;
+    HIPCHK(c, reduce_counts(c, L, f.fs));
+    HIPCHK(c, hipEventRecord(f.ev[EV_DONE], f.fs));
+    c->last_done = f.ev[EV_DONE];
+    L.scene = f.scene; L.gen = f.frame_gen; L.done = f.ev[EV_DONE]; L.prevgeo = f.prevgeo_read;
+    c->geo_last = f.scene->geo_gen; c->geo_last_scene = f.scene;
+    if (f.fs == c->stream && c->ahead > 0) L.wait = f.ev[EV_DONE];
+    if (f.fs != c->stream) HIPCHK(c, hipStreamWaitEvent(c->stream, f.ev[EV_DONE], 0));   // sequential semantics
     record_traversal_time(c);
-    c->r_last = c->rcur;   // reservoirsLastFrame = final buffer (pointer swap, :477)
+    c->r_last = f.rcur;   // reservoirsLastFrame = final buffer (pointer swap, :477)
     c->frames++;
-    c->active = false;
-    if (band_rgb) *band_rgb = c->fb + 3 * (size_t)c->F.y0 * c->W;
+    f.active = false;
+    if (band_rgb) *band_rgb = L.fb + 3 * (size_t)f.F.y0 * c->W;
     if (t) {
-        HIPCHK(c, hipMemcpyAsync(c->h_cnt, c->d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, c->fs));
-        HIPCHK(c, hipStreamSynchronize(c->fs));
-        float a = 0, b = 0, d = 0, e = 0, f = 0, tot = 0;
-        hipEventElapsedTime(&a, c->ev[EV_BEGIN], c->ev[EV_INIT]);
-        hipEventElapsedTime(&b, c->ev[EV_INIT], c->ev[EV_VIS]);
-        hipEventElapsedTime(&d, c->ev[EV_VIS], c->ev[EV_TEMPORAL]);
-        hipEventElapsedTime(&e, c->ev[EV_TEMPORAL], c->ev[EV_SPATIAL]);
-        hipEventElapsedTime(&f, c->ev[EV_SPATIAL], c->ev[EV_SHADE]);
-        hipEventElapsedTime(&tot, c->ev[EV_BEGIN], c->ev[EV_SHADE]);
-        t->gbuffer_initial_ms = a; t->visibility_ms = b; t->temporal_ms = d; t->spatial_ms = e; t->shade_ms = f;
-        t->total_ms = tot; t->rays = c->h_cnt->rays; t->primary_rays = c->h_cnt->primary;
+        HIPCHK(c, hipMemcpyAsync(c->h_cnt, L.cnt, sizeof(Counters), hipMemcpyDeviceToHost, f.fs));
+        HIPCHK(c, hipStreamSynchronize(f.fs));
+        float v[6];
+        pass_times(f.ev, v);
+        t->gbuffer_initial_ms = v[0]; t->visibility_ms = v[1]; t->temporal_ms = v[2]; t->spatial_ms = v[3]; t->shade_ms = v[4];
+        t->total_ms = v[5]; t->rays = c->h_cnt->rays; t->primary_rays = c->h_cnt->primary;
         t->reproj_outside = c->h_cnt->reproj_outside;
-        fold_slot(c, c->slot);
+        fold_slot(c, f.slot);
     }
     return RS_OK;
 }
 
 extern "C" int rs_get_timing_totals(rs_context* c, rs_pass_times* sum, uint32_t* n_frames, int reset) {
     if (!c || !sum) return fail(c, RS_E_INVALID, "rs_get_timing_totals: null argument");
-    if (c->active) return fail(c, RS_E_INVALID, "rs_get_timing_totals: a frame is in flight");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_get_timing_totals: a frame is in flight");
     HIPCHK(c, enter(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int s = 0; s < rs_context::kEvRing; ++s) fold_slot(c, s);
@@ -1999,7 +1979,7 @@ extern "C" int rs_render_frame(rs_context* c, const rs_scene* s, const rs_camera
             if ((rc = rs_tile_spatial(c, i))) return rc;
     if ((rc = rs_tile_finish(c, nullptr, times))) return rc;
     if (frame_rgb_host) {
-        HIPCHK(c, hipMemcpyAsync(frame_rgb_host, c->fb, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost,
+        HIPCHK(c, hipMemcpyAsync(frame_rgb_host, c->lane().fb, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost,
                                  c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
@@ -2008,7 +1988,7 @@ extern "C" int rs_render_frame(rs_context* c, const rs_scene* s, const rs_camera
 
 // The ground-truth renders (rs_mis.h, rs_path.h) into the framebuffer: one launch on the context's stream, spp
 // samples per pixel.  Does not touch the ReSTIR history (G-buffers, reservoirs, frame counter).  launch(T, S, F,
-// grid, slot) enqueues the kernel of traversal kind T on c->fs and returns its hipError_t.
+// grid, slot) enqueues the kernel of traversal kind T on c->fr.fs and returns its hipError_t.
 template <class Launch>
 static int render_ground_truth(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
                                uint32_t frame_index, uint32_t spp, float* frame_rgb_host, rs_pass_times* t,
@@ -2016,45 +1996,38 @@ static int render_ground_truth(rs_context* c, const rs_scene* s, const rs_camera
     const std::string fn = who;
     if (!c || !s || !cam || !P) return fail(c, RS_E_INVALID, fn + ": null argument");
     if (s->ctx != c) return fail(c, RS_E_INVALID, fn + ": scene belongs to another context");
-    if (c->active) return fail(c, RS_E_INVALID, fn + ": a tile frame is in flight");
+    if (c->fr.active) return fail(c, RS_E_INVALID, fn + ": a tile frame is in flight");
     if (P->use_skybox && s->sky < 0)
         return fail(c, RS_E_UNSUPPORTED, "use_skybox: the scene has no sky map (rs_scene_set_sky / rs_scene_load_sky)");
     if (spp < 1 || spp > 65536) return fail(c, RS_E_INVALID, fn + ": spp must be in [1, 65536]");
     HIPCHK(c, enter(c));
-    FrameConst F = {};
-    F.bg = vec3{P->bg_color[0], P->bg_color[1], P->bg_color[2]};
-    F.tnear_off = P->tnear_offset; F.tfar_off = P->tfar_offset; F.normal_off = P->normal_offset;
-    F.use_sky = P->use_skybox ? 1 : 0;
-    F.seed = P->seed; F.frame = frame_index;
-    F.W = c->W; F.H = c->H; F.y0 = 0; F.y1 = c->H; F.gy0 = 0; F.gy1 = c->H;
+    FrameConst F = frame_const_base(c, P, frame_index, 0, c->H, 0, c->H);
     GCam gc;
     make_camera(cam, c->H, gc, F.inv_view);
     F.cam = gc; F.camp = gc;
     const DevScene S = s->dev();
     const dim3 g = grid_rows(c->W, 0, c->H);
-    c->fs = c->stream; c->li = 0;                 // the context's stream (after every frame enqueued so far)
-    c->d_cnt = c->cnts[0]; c->d_red = c->reds[0];
+    Frame& f = c->fr;
+    f.fs = c->stream; f.li = 0;                   // the context's stream (after every frame enqueued so far), lane 0
+    Lane& L = c->lanes[0];
     sync_all(c);                                  // lane 0's slots may still be in use
-    c->fb = c->fbs[0];
-    if (c->fb_read[0]) { HIPCHK(c, hipEventSynchronize(c->fb_read[0])); c->fb_read[0] = nullptr; }
-    if (!use_parts(c, 0, grid_waves(g))) return fail(c, RS_E_HIP, "hipMalloc(count slots) failed");
+    if (L.fb_read) { HIPCHK(c, hipEventSynchronize(L.fb_read)); L.fb_read = nullptr; }
+    if (!use_parts(c, L, grid_waves(g))) return fail(c, RS_E_HIP, "hipMalloc(count slots) failed");
     c->join_next = true;
-    HIPCHK(c, hipMemsetAsync(c->d_cnt, 0, sizeof(Counters), c->stream));
+    HIPCHK(c, hipMemsetAsync(L.cnt, 0, sizeof(Counters), c->stream));
     hipEvent_t e0 = c->ev_gt[0], e1 = c->ev_gt[1];
     HIPCHK(c, hipEventRecord(e0, c->stream));
     pick_traversal(c, s);
-    c->twide = s->wide_on;
-    c->tuning = false;               // the ReSTIR frames own the per-scene traversal tuning
-    HIPCHK(c, with_trav(c, [&](auto T) { return launch(T, S, F, g, count_slot(c, g)); }));
+    f.twide = s->wide_on;
+    f.tuning = false;                // the ReSTIR frames own the per-scene traversal tuning
+    HIPCHK(c, with_trav(c, [&](auto T) { return launch(T, S, F, g, count_slot(c, L, g)); }));
     HIPCHK(c, hipEventRecord(e1, c->stream));
-    k_reduce_counts<<<kReduceBlocks, kReduceThreads, 0, c->stream>>>(c->d_part, c->part_used, c->d_red,
-                                                                     (unsigned*)(c->d_red + kReduceBlocks), c->d_cnt, c->d_tot);
-    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, reduce_counts(c, L, c->stream));
     if (t || frame_rgb_host) {
         if (frame_rgb_host)
-            HIPCHK(c, hipMemcpyAsync(frame_rgb_host, c->fb, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost,
+            HIPCHK(c, hipMemcpyAsync(frame_rgb_host, L.fb, (size_t)c->W * c->H * 3 * sizeof(float), hipMemcpyDeviceToHost,
                                      c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_cnt, c->d_cnt, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_cnt, L.cnt, sizeof(Counters), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (t) {
             float ms = 0;
@@ -2072,7 +2045,7 @@ extern "C" int rs_render_direct_mis(rs_context* c, const rs_scene* s, const rs_c
                                     uint32_t frame_index, uint32_t spp, float* frame_rgb_host, rs_pass_times* t) {
     return render_ground_truth(c, s, cam, P, frame_index, spp, frame_rgb_host, t, "rs_render_direct_mis",
                                [&](auto T, const DevScene& S, const FrameConst& F, dim3 g, CountSlot slot) {
-        k_direct_mis<T()><<<g, 256, 0, c->fs>>>(S, F, (int)spp, c->fb, slot);
+        k_direct_mis<T()><<<g, 256, 0, c->fr.fs>>>(S, F, (int)spp, c->lane().fb, slot);
         return hipGetLastError();
     });
 }
@@ -2094,14 +2067,14 @@ extern "C" int rs_render_path(rs_context* c, const rs_scene* s, const rs_camera*
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
         }
-        k_path_nee<T()><<<g, kPathBlock, lds, c->fs>>>(S, F, Q, c->fb, slot);
+        k_path_nee<T()><<<g, kPathBlock, lds, c->fr.fs>>>(S, F, Q, c->lane().fb, slot);
         return hipGetLastError();
     });
 }
 
 extern "C" int rs_get_frame_device_ptr(rs_context* c, const float** dptr) {
     if (!c || !dptr) return fail(c, RS_E_INVALID, "rs_get_frame_device_ptr: null argument");
-    *dptr = c->fb;
+    *dptr = c->lane().fb;
     return RS_OK;
 }
 
@@ -2118,7 +2091,7 @@ __global__ void __launch_bounds__(256) k_readback(const rb_v4* __restrict__ src,
 
 extern "C" int rs_frame_readback(rs_context* c, float* dst, uint64_t* ticket) {
     if (!c || !dst || !ticket) return fail(c, RS_E_INVALID, "rs_frame_readback: null argument");
-    if (c->active) return fail(c, RS_E_INVALID, "rs_frame_readback: a tile frame is in flight");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_frame_readback: a tile frame is in flight");
     HIPCHK(c, enter(c));
     if (!c->rb_ev[0])
         for (int i = 0; i < rs_context::kRb; ++i) HIPCHK(c, hipEventCreateWithFlags(&c->rb_ev[i], hipEventDisableTiming));
@@ -2133,19 +2106,19 @@ extern "C" int rs_frame_readback(rs_context* c, float* dst, uint64_t* ticket) {
     // queues with a lane and serialise the copy with that lane's next frame.
     hipPointerAttribute_t at{};
     void* ddst = nullptr;
-    const bool kernel_ok = c->readback_kernel && bytes % 16 == 0 && ((uintptr_t)dst & 15) == 0 &&
+    const bool kernel_ok = c->sw.readback_kernel && bytes % 16 == 0 && ((uintptr_t)dst & 15) == 0 &&
                            hipPointerGetAttributes(&at, dst) == hipSuccess && at.type == hipMemoryTypeHost &&
                            hipHostGetDevicePointer(&ddst, dst, 0) == hipSuccess && ddst != nullptr;
     (void)hipGetLastError();                   // a pageable pointer leaves an error in the per-thread slot
     if (kernel_ok) {
-        k_readback<<<256, 256, 0, c->stream>>>((const rb_v4*)c->fb, (rb_v4*)ddst, bytes / 16);
+        k_readback<<<256, 256, 0, c->stream>>>((const rb_v4*)c->lane().fb, (rb_v4*)ddst, bytes / 16);
         HIPCHK(c, hipGetLastError());
     } else {
-        HIPCHK(c, hipMemcpyAsync(dst, c->fb, bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dst, c->lane().fb, bytes, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipEventRecord(c->rb_ev[k], c->stream));
     c->rb_busy[k] = true;
-    c->fb_read[c->li] = c->rb_ev[k];
+    c->lane().fb_read = c->rb_ev[k];
     *ticket = t;
     return RS_OK;
 }
@@ -2188,11 +2161,8 @@ extern "C" int rs_dump_gbuffer(rs_context* c, int prev, float* out) {
     size_t n = (size_t)c->W * c->H;
     const GBuf& g = c->G[prev ? c->gprev : c->gcur];
     std::vector<float4> a(n), b(n), d(n), e(n), f(n);
-    HIPCHK(c, hipMemcpyAsync(a.data(), g.g0, n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(b.data(), g.g1, n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d.data(), g.g2, n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(e.data(), g.g3, n * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(f.data(), g.g4, n * 16, hipMemcpyDeviceToHost, c->stream));
+    const std::pair<std::vector<float4>*, const float4*> cp[5] = {{&a, g.g0}, {&b, g.g1}, {&d, g.g2}, {&e, g.g3}, {&f, g.g4}};
+    for (const auto& q : cp) HIPCHK(c, hipMemcpyAsync(q.first->data(), q.second, n * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (size_t p = 0; p < n; ++p) {
         float* o = out + 19 * p;
@@ -2226,7 +2196,7 @@ extern "C" int rs_dump_reservoirs(rs_context* c, float* out) {
 extern "C" int rs_post_frame(rs_context* c, const rs_post_params* pp, const float** display_rgba_dptr,
                              rs_post_stats* stats) {
     if (!c || !pp) return fail(c, RS_E_INVALID, "rs_post_frame: null argument");
-    if (c->active) return fail(c, RS_E_INVALID, "rs_post_frame: a frame is in flight (finish it first)");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_post_frame: a frame is in flight (finish it first)");
     HIPCHK(c, enter(c));
     const size_t npx = (size_t)c->W * c->H;
     const int nblk_max = (int)((npx + 255) / 256);
@@ -2239,7 +2209,7 @@ extern "C" int rs_post_frame(rs_context* c, const rs_post_params* pp, const floa
         HIPCHK(c, hipMalloc(&c->post_out, sizeof(double2)));
     }
     // rows of the last rendered frame / band (rs_render_frame: all rows)
-    const int y0 = c->frames ? c->F.y0 : 0, y1 = c->frames ? c->F.y1 : c->H;
+    const int y0 = c->frames ? c->fr.F.y0 : 0, y1 = c->frames ? c->fr.F.y1 : c->H;
     // a denoised display is validated before the accumulator blends this frame (a rejected call leaves the
     // accumulator and accFrameCtr as they were)
     if (pp->denoise && !c->denoiser) return fail(c, RS_E_INVALID, "rs_post_frame: denoise without a denoiser (rs_context_set_denoiser)");
@@ -2248,7 +2218,7 @@ extern "C" int rs_post_frame(rs_context* c, const rs_post_params* pp, const floa
     const size_t n = (size_t)(y1 - y0) * c->W;
     const int nblk = (int)((n + 255) / 256);
     if (nblk > 0) {
-        k_post<<<nblk, 256, 0, c->stream>>>(c->fb, c->acc, c->display, P, c->post_part);
+        k_post<<<nblk, 256, 0, c->stream>>>(c->lane().fb, c->acc, c->display, P, c->post_part);
         HIPCHK(c, hipGetLastError());
         k_post_reduce<<<1, 256, 0, c->stream>>>(c->post_part, nblk, c->post_out);
         HIPCHK(c, hipGetLastError());
@@ -2313,7 +2283,7 @@ extern "C" int rs_export_png(rs_context* c, const char* path, const rs_export_pa
         const double mean = n > 0 ? st.x / n : 0.0, var = n > 0 ? st.y / n - mean * mean : 0.0;
         std::FILE* f = std::fopen((std::string(path) + ".txt").c_str(), "w");
         if (!f) return fail(c, RS_E_IO, std::string("rs_export_png: cannot write ") + path + ".txt");
-        const rs_frame_params& P = c->P;
+        const rs_frame_params& P = c->fr.P;
         std::ostringstream o;
         o << "Image name: " << path << "\n\n";
         o << "Iteration count: " << c->acc_frames << "\n";
@@ -2348,7 +2318,7 @@ extern "C" int rs_image_encode_png(const char* path, uint32_t w, uint32_t h, uin
 extern "C" int rs_denoise_frame(rs_context* c, rs_denoiser* d, const rs_denoise_params* p, const float** out) {
     if (!c || !d || !out) return fail(c, RS_E_INVALID, "rs_denoise_frame: null argument");
     if (rs::denoiser_ctx(d) != c) return fail(c, RS_E_INVALID, "rs_denoise_frame: the denoiser belongs to another context");
-    if (c->active) return fail(c, RS_E_INVALID, "rs_denoise_frame: a frame is in flight (finish it first)");
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_denoise_frame: a frame is in flight (finish it first)");
     if (!c->acc || !c->frames) return fail(c, RS_E_INVALID, "rs_denoise_frame: no accumulator yet (render a frame and call rs_post_frame)");
     if (p && !p->hdr) return fail(c, RS_E_UNSUPPORTED, "rs_denoise_frame: only hdr = true (the reference's setting) is supported");
     HIPCHK(c, enter(c));

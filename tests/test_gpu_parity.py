@@ -300,6 +300,49 @@ def test_run_ahead_bit_identical(which):
             _assert_close(out[2][f], o.render(os_, cam(f), prm, f), f"{which} run-ahead frame {f}")
 
 
+def test_run_ahead_sequencing_bit_identical():
+    """The host sequencing no other test crosses, in one run: traversal left on AUTO (six tuning frames on the
+    context's stream with their row-cost recording, then the tile-row order) with frames in flight, the depth changed
+    2 -> 0 -> 1 -> 2 between frames, pipelined position updates on most frames, one in-place update with normals, and
+    a ground-truth render (lane 0, the context's stream) between two ReSTIR frames.  Every ReSTIR frame equals, bit
+    for bit, the same calls on a renderer pinned to lockstep walks at depth 0 (both walk kinds give identical frames:
+    test_traversal_kinds_bit_identical; the row order only changes dispatch order)."""
+    import torch
+    from restir_amd.distributed import _CudaBuf
+    W, H, n_frames = 96, 64, 12
+    sc, prm = scenes.cornell_many_lights(256), P.c3_params(m_area=6)
+    assert prm.do_temporal and prm.do_spatial
+    cam = lambda f: scenes.orbit_camera(sc.camera, f, 48, 0.2)
+    depth_at = {0: 2, 6: 0, 8: 1, 10: 2}
+    torch.cuda.set_stream(torch.cuda.Stream())       # the clones below are ordered on the frames' stream
+    st = torch.cuda.current_stream().cuda_stream
+    out = {}
+    for run in ("lockstep0", "sequenced"):
+        g = Renderer(W, H, stream=st)
+        if run == "lockstep0":
+            g.set_traversal("lockstep")
+            g.set_run_ahead(0)
+        gs = g.load_scene(sc)
+        frames = []
+        for f in range(n_frames):
+            if run == "sequenced" and f in depth_at:
+                g.set_run_ahead(depth_at[f])
+            if f == 5:
+                g.render_direct_mis(gs, cam(f), prm, f, spp=1, copy_out=False)
+            if f == 7:
+                gs.update_positions(scenes.moving_light_positions(sc, f, 48), sc.normals)   # in place, with normals
+            elif f not in (0, 3):
+                gs.update_positions(scenes.moving_light_positions(sc, f, 48), None)         # pipelined at depth > 0
+            g.produce_restir(gs, cam(f), prm, f, copy_out=False, timed=False)
+            frames.append(torch.as_tensor(_CudaBuf(g.frame_device_ptr(), W * H * 12, "<f4", 4), device="cuda").clone())
+        out[run] = [t.cpu().numpy().reshape(H, W, 3) for t in frames]
+        if run == "sequenced":
+            assert g.traversal(gs)[2] in (0, 1),"the six tuning frames did not settle the scene's traversal kind"
+    for f in range(n_frames):
+        assert np.isfinite(out["sequenced"][f]).all() and out["sequenced"][f].any()
+        assert np.array_equal(out["lockstep0"][f], out["sequenced"][f]), f"frame {f}"
+
+
 def test_spatial_reuse_variance_matches_oracle():
     """SURVEY.md §8(c) / north star: spatial-reuse variance -- per-pixel variance over 64 frame indices
     (static camera, temporal off, metric point), averaged over non-emissive pixels -- within [0.95, 1.05]
