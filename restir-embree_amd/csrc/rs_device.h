@@ -226,13 +226,22 @@ __device__ __forceinline__ ShadeFrame make_frame(const GElem& g, vec3 cam) {
 __device__ __forceinline__ bool is_phong(int type) { return type == MT_PHONG || type == MT_DIELECTRIC; }
 // MaterialPhong::evalPdf -- the MIS pdf is always Phong's (pg/ReSTIRIntegrator.h:54-59,
 // pg/MaterialPhong.cpp:150-172)
-// Lambert surfaces (ks = 0: omp = 0) add the lobe term a * pow(..) * 0 = +0 exactly (a finite, the pow in
-// [0, 1]), so the powf is skipped for them -- the MIS pdf of every area candidate on a diffuse wall
+// Lambert surfaces (ks = 0: omp = 0) add the lobe term a * pow(..) * 0 = +0 exactly, so the powf is skipped for
+// them -- the MIS pdf of every area candidate on a diffuse wall.  Exactly +0 needs a and the pow finite, which is
+// what kLobeSkipMax bounds: for shininess in [+0, 1e8] a <= 1.6e7 and the pow's base, the dot of two normalised
+// vectors, is at most 1 + 6e-7, so the pow is at most e^60.  Outside that range the term is evaluated as the
+// reference evaluates it: a negative shininess (a float roughness texel above 1 gives 2 / r^2 - 2 < 0) makes
+// pow(0, n) = +inf, +inf shininess (a roughness texel of 0) makes a = +inf, and either times 0 is the NaN that
+// blackens the reference's pixel.  The range test is one unsigned compare of the float's bits: the floats from +0
+// up order as their bit patterns, and every negative float (-0 too, harmlessly), infinity and NaN has a larger one.
+// (Measured, DESIGN.md section 5: a flag computed once per pixel in make_frame costs the initial pass registers.)
 // (Call: the pow's core as a called function, rs_libm.h rs_powf_sel -- for the register-bound per-lane kernels)
+constexpr uint32_t kLobeSkipMax = 0x4cbebc20u;          // the bits of 1e8f
 template <bool Call = false>
 __device__ __forceinline__ float phong_pdf(const ShadeFrame& s, vec3 wi) {
     float pdf = gmax(dot(s.nrm, wi), 0.0f) * kOneOverPi * s.pf;
-    pdf += (s.omp != 0.0f || !isfinite(s.a)) ? s.a * rs_powf_sel(gmax(0.0f, dot(wi, s.wr)), s.shin, Call) * s.omp : 0.0f;
+    const bool lobe = s.omp != 0.0f || __float_as_uint(s.shin) > kLobeSkipMax;
+    pdf += lobe ? s.a * rs_powf_sel(gmax(0.0f, dot(wi, s.wr)), s.shin, Call) * s.omp : 0.0f;
     return pdf;
 }
 // BRDF eval dispatch (pg/ReSTIRIntegrator.h:32-41): Phong for PHONG/DIELECTRIC

@@ -252,6 +252,15 @@ __device__ __forceinline__ vec3 evaluate_f_post(const FPre& p, bool occ) {
     if (p.need) L = L * (float)(!occ);
     return p.ok ? L : mk(0, 0, 0);
 }
+// The RIS weight m * p-hat * W of a candidate that is not lit, bit for bit what evaluate_f_post and length give:
+// p-hat = |0| for a candidate that is not ok and |L * 0| for an occluded one -- +0 for a finite L, NaN for an L with
+// an infinite or NaN channel (a negative shininess makes the lobe's pow(0, n) infinite), as the reference's L * V
+// is then.  The three products are exact (+-0 or NaN), so their fused sum is +-0 or NaN exactly where the length
+// of L * 0 is +0 or NaN.
+__device__ __forceinline__ float unlit_weight(float m, const FPre& p, float Wc) {
+    const float z = p.ok ? fabsf(fmaf(p.L.x, 0.0f, fmaf(p.L.y, 0.0f, p.L.z * 0.0f))) : 0.0f;
+    return m * z * Wc;
+}
 template <int T>
 __device__ __forceinline__ vec3 evaluate_f(const DevScene& S, const FrameConst& F, const Sample& s, vec3 pos,
                                            bool emissive, const ShadeFrame& sf, bool test_vis, bool alive,
@@ -526,9 +535,9 @@ struct FrameSlot {
 
 // One batch of area candidates [c0, c0 + kB) (initialRenderPass :246-266): sample, unoccluded f, one
 // walk for the batch's shadow rays; returns each candidate's RIS weight w in w_out.  Only two weights per
-// candidate stay live across the walk -- the unoccluded one and the occluded one, (m * 0) * W -- instead
-// of the sample, f, MIS weight and W: an occluded (or invalid) candidate has f = 0 and p-hat = 0, which
-// both produce bit for bit.  (The selected candidate's f is re-derived from its re-drawn sample.)
+// candidate stay live across the walk -- the unoccluded one and the unlit one (unlit_weight) -- instead
+// of the sample, f, MIS weight and W: an invalid candidate has f = 0 and an occluded one f = L * 0, whose
+// p-hat both weights hold bit for bit.  (The selected candidate's f is re-derived from its re-drawn sample.)
 template <int T, int kB>
 __device__ __forceinline__ void area_batch(const DevScene& S, const FrameConst& F, vec3 pos, const ShadeFrame& sf,
                                            Rng& rng, int c0, int c_end, bool alive, bool tv, const uint32_t* pick,
@@ -547,7 +556,7 @@ __device__ __forceinline__ void area_batch(const DevScene& S, const FrameConst& 
         const float ph = length(p.L);
         const float m = F.m_brdf > 0 ? mis : inv_ma;
         wu[k] = m * ph * Wc;
-        wo[k] = m * 0.0f * Wc;
+        wo[k] = unlit_weight(m, p, Wc);
         act[k] = p.need; okb[k] = p.ok; dir[k] = p.dir; tf[k] = p.tfar; occ[k] = false;
         rays += act[k] ? 1u : 0u;
     }
@@ -579,7 +588,7 @@ __device__ __forceinline__ void area_batch_px(const DevScene& S, const FrameCons
         const float ph = length(p.L);
         const float m = F.m_brdf > 0 ? mis : inv_ma;
         wu[k] = m * ph * Wc;
-        wo[k] = m * 0.0f * Wc;
+        wo[k] = unlit_weight(m, p, Wc);
         need |= p.need ? 1u << k : 0u;
         ok |= p.ok ? 1u << k : 0u;
         dir[k] = p.dir; tf[k] = p.tfar;
@@ -927,7 +936,7 @@ __device__ __forceinline__ AreaCand area_cand(const DevScene& S, const FrameCons
     a.bucket = ray_bucket(S, a.pick, pr.dir);
     const float m = F.m_brdf > 0 ? mis : inv_ma;
     a.wu = m * length(pr.L) * Wc;
-    const float wo = m * 0.0f * Wc;             // +-0 (the same reservoir update) or NaN
+    const float wo = unlit_weight(m, pr, Wc);   // +-0 (the same reservoir update) or NaN
     a.wo_nan = wo != wo;
     a.ok = pr.ok;
     a.need = pr.need;

@@ -3,7 +3,8 @@ tests/test_gpu_closed_form.py on the HIP renderer).  TEST INFRASTRUCTURE ONLY.
 
 Everything the estimators are compared with here is float64 numpy written from the rendering equation, not from
 the oracle: Lambert's polygon formula, a stratified quadrature with brute-force visibility, and the furnace value
-(kd + ks) Le.  The module shares no code with oracle/restir_oracle.c and never calls it; the test files hand it a
+(kd + ks) Le (kd Le for the material types whose eval is Lambert's).  The module shares no code with
+oracle/restir_oracle.c and never calls it; the test files hand it a
 `backend` (the oracle or the GPU renderer) that it drives through two methods:
 
     backend.gbuffer(cf)                          -> (H, W, 19) G-buffer of cf.scene seen from cf.camera
@@ -45,8 +46,10 @@ UMBRA_BOUND = 1e-3
 
 LE = (10.0, 6.0, 3.0)
 FURNACE_LE = (2.0, 2.0, 2.0)
-FRAMES = {"open": 192, "blocked": 192, "furnace_steep": 96, "furnace_grazing": 96}
-MIS_SPP = {"open": 256, "blocked": 256, "furnace_steep": 512, "furnace_grazing": 512}
+FRAMES = {"open": 192, "blocked": 192, "furnace_steep": 96, "furnace_grazing": 96, "furnace_types_steep": 96,
+          "furnace_types_grazing": 96}
+MIS_SPP = {"open": 256, "blocked": 256, "furnace_steep": 512, "furnace_grazing": 512, "furnace_types_steep": 512,
+           "furnace_types_grazing": 512}
 # cases whose 4 SE at the frame counts above exceeded SUM_CAP: more frames, not a wider bound
 MORE_FRAMES = {("blocked", "debias_contrib_T1"): 2304, ("furnace_steep", "pairwise_T1"): 256,
                ("furnace_grazing", "pairwise_T1"): 256}
@@ -76,6 +79,7 @@ ESTIMATORS["pairwise_T1_vis"] = _restir(do_spatial=1, do_temporal=1, spatial_mis
 ESTIMATORS["balance_T1_2pass_reject"] = _restir(do_spatial=1, do_temporal=1, spatial_mis="balance", spatial_passes=2,
                                                 reject_dissimilar=1)
 FURNACE_ESTIMATORS = ("mis", "path_nogi", "initial", "balance_T0", "pairwise_T1")
+FURNACE_SCENES = ("furnace_steep", "furnace_grazing", "furnace_types_steep", "furnace_types_grazing")
 
 
 # ---------------------------------------------------------------- scenes
@@ -143,6 +147,17 @@ STRIPS = {
     "phong_n500": scenes.Material(kd=(0.4, 0.35, 0.3), ks=(0.3, 0.3, 0.3), shininess=500.0, type=scenes.PHONG),
 }
 KD_KS_STRIPS = ("phong_n1", "phong_n8", "phong_n500")
+# One strip per class of material types (tests/material_cases.py CLASSES): only PHONG and DIELECTRIC evaluate the
+# specular term, so every other type reflects kd Le whatever its ks -- which its BRDF sampling still uses.
+_KD, _KS = (0.4, 0.35, 0.3), (0.3, 0.3, 0.3)
+TYPE_STRIPS = {
+    "lambert": scenes.Material(kd=(0.5, 0.4, 0.3), type=scenes.LAMBERT),
+    "normal": scenes.Material(kd=_KD, ks=_KS, shininess=8.0, type=scenes.NORMAL),
+    "mirror": scenes.Material(kd=_KD, ks=_KS, shininess=8.0, type=scenes.MIRROR),
+    "dielectric": scenes.Material(kd=_KD, ks=_KS, shininess=8.0, type=scenes.DIELECTRIC),
+    "transparent": scenes.Material(kd=_KD, ks=(0.6, 0.6, 0.6), shininess=64.0, type=scenes.DIELECTRIC_TRANSPARENT),
+}
+PHONG_EVAL_TYPES = (scenes.PHONG, scenes.DIELECTRIC)
 
 
 def _icosphere(subdiv):
@@ -171,12 +186,13 @@ def _icosphere(subdiv):
     return np.asarray(v), np.asarray(f)
 
 
-def furnace_scene(camera="steep"):
+def furnace_scene(camera="steep", strips=None, name=None):
     """Icosphere of radius 2 (320 triangles, flat normals pointing inward, every one emitting FURNACE_LE) around five
     coplanar strips at z = 0, 0.3 wide in x, side by side."""
     cam, width, height = FURNACE_CAMERAS[camera]
+    strips = STRIPS if strips is None else strips
     b = scenes._Builder()
-    for i, m in enumerate(STRIPS.values()):
+    for i, m in enumerate(strips.values()):
         x0, x1 = -0.75 + 0.3 * i, -0.45 + 0.3 * i
         b.quad([x0, -0.6, 0], [x1, -0.6, 0], [x1, 0.8, 0], [x0, 0.8, 0], b.material(m))
     v, f = _icosphere(2)
@@ -186,13 +202,27 @@ def furnace_scene(camera="steep"):
     n /= np.linalg.norm(n, axis=1, keepdims=True)
     n *= -np.sign((n * t64.mean(axis=1)).sum(-1))[:, None]      # inward
     b.tris(tri.reshape(-1, 9), np.repeat(n, 3, axis=0).reshape(-1, 9), b.material(scenes.Material(le=FURNACE_LE)))
-    return _finish(b, cam, f"furnace_{camera}", width, height, dict(STRIPS))
+    return _finish(b, cam, name or f"furnace_{camera}", width, height, dict(strips))
+
+
+def furnace_types_scene(camera, dielectric_as=scenes.DIELECTRIC):
+    """The furnace with TYPE_STRIPS; dielectric_as = PHONG re-types the DIELECTRIC strip inside its class."""
+    strips = dict(TYPE_STRIPS)
+    name = f"furnace_types_{camera}"
+    if dielectric_as != scenes.DIELECTRIC:
+        strips["dielectric"] = scenes.Material(**{**vars(strips["dielectric"]), "type": dielectric_as})
+        name += f"_dielectric_as_{dielectric_as}"
+    return furnace_scene(camera, strips, name)
 
 
 @functools.lru_cache(maxsize=None)
 def get_scene(name):
     return {"open": open_scene, "blocked": blocked_scene, "furnace_steep": lambda: furnace_scene("steep"),
-            "furnace_grazing": lambda: furnace_scene("grazing")}[name]()
+            "furnace_grazing": lambda: furnace_scene("grazing"),
+            "furnace_types_steep": lambda: furnace_types_scene("steep"),
+            "furnace_types_grazing": lambda: furnace_types_scene("grazing"),
+            "furnace_types_steep_swapped": lambda: furnace_types_scene("steep", scenes.PHONG),
+            "furnace_types_grazing_swapped": lambda: furnace_types_scene("grazing", scenes.PHONG)}[name]()
 
 
 # ---------------------------------------------------------------- references
@@ -272,10 +302,13 @@ def polygon_radiance(cf, x, n, kd):
     return kd / np.pi * e
 
 
-def furnace_expected(kd, ks, le):
+def furnace_expected(kd, ks, le, mtype=scenes.PHONG):
     """Direct radiance of a Phong surface whose specular term is divided by I_M = the integral of (wi . wr)^n cos(theta)
-    over the hemisphere, under uniform incident radiance Le: (kd + ks) Le for every view, exponent and tessellation."""
-    return (np.asarray(kd, np.float64) + np.asarray(ks, np.float64)) * np.asarray(le, np.float64)
+    over the hemisphere, under uniform incident radiance Le: (kd + ks) Le for every view, exponent and tessellation.
+    Only the types PHONG and DIELECTRIC evaluate that term; every other type (mtype: scalar or (N,)) reflects kd Le."""
+    phong = np.isin(np.asarray(mtype), PHONG_EVAL_TYPES)
+    ks = np.where(phong[..., None], np.asarray(ks, np.float64), 0.0)
+    return (np.asarray(kd, np.float64) + ks) * np.asarray(le, np.float64)
 
 
 def validate(cf, x, n):
@@ -330,11 +363,12 @@ def reference(cf, g):
     x, n, kd, ks = g[mask][:, 0:3], g[mask][:, 3:6], g[mask][:, 6:9], g[mask][:, 9:12]
     img = np.zeros(mask.shape)
     if cf.name.startswith("furnace"):
-        img[mask] = furnace_expected(kd, np.where(g[mask][:, 17:18] == scenes.PHONG, ks, 0.0), FURNACE_LE).sum(-1)
+        img[mask] = furnace_expected(kd, ks, FURNACE_LE, g[mask][:, 17]).sum(-1)
         regions = {}
         for name, m in cf.strips.items():
             mf = np.array([*m.kd, *m.ks], np.float32).astype(np.float64)
-            regions[name] = mask & (np.abs(g[..., 6:12] - mf).max(-1) == 0) & (g[..., 15] == np.float32(m.shininess))
+            regions[name] = mask & (np.abs(g[..., 6:12] - mf).max(-1) == 0) & (g[..., 15] == np.float32(m.shininess)) \
+                & (g[..., 17] == m.type)
         return Reference(mask, img, regions, None, x, n)
     rad, vis = quadrature_radiance(cf, x, n, kd, visibility=True)
     img[mask] = rad.sum(-1)
@@ -468,6 +502,57 @@ MEASURED = {
     "furnace_grazing/pairwise_T1/phong_n8": (0.9997, 0.00444, 0.0046, 0.0214),
     "furnace_grazing/pairwise_T1/spec_n64": (1.0021, 0.00620, 0.0101, 0.0344),
     "furnace_grazing/pairwise_T1/phong_n500": (1.0025, 0.00508, 0.0128, 0.0500),
+    # the type strips (TYPE_STRIPS), measured as the rows above
+    "furnace_types_steep/mis/lambert": (1.0009, 0.00076, 0.0040, 0.0153),
+    "furnace_types_steep/mis/normal": (0.9997, 0.00096, 0.0040, 0.0152),
+    "furnace_types_steep/mis/mirror": (1.0001, 0.00074, 0.0045, 0.0140),
+    "furnace_types_steep/mis/dielectric": (0.7086, 0.00101, 0.2936, 0.3170),
+    "furnace_types_steep/mis/transparent": (1.0007, 0.00083, 0.0040, 0.0128),
+    "furnace_types_steep/path_nogi/lambert": (1.0009, 0.00076, 0.0040, 0.0153),
+    "furnace_types_steep/path_nogi/normal": (0.9997, 0.00096, 0.0040, 0.0152),
+    "furnace_types_steep/path_nogi/mirror": (1.0001, 0.00074, 0.0045, 0.0140),
+    "furnace_types_steep/path_nogi/dielectric": (0.7086, 0.00101, 0.2936, 0.3170),
+    "furnace_types_steep/path_nogi/transparent": (1.0007, 0.00083, 0.0040, 0.0128),
+    "furnace_types_steep/initial/lambert": (0.9997, 0.00200, 0.0147, 0.0535),
+    "furnace_types_steep/initial/normal": (1.0010, 0.00291, 0.0119, 0.0480),
+    "furnace_types_steep/initial/mirror": (0.9999, 0.00246, 0.0141, 0.0496),
+    "furnace_types_steep/initial/dielectric": (0.9982, 0.00348, 0.0164, 0.0647),
+    "furnace_types_steep/initial/transparent": (0.9975, 0.00297, 0.0196, 0.0670),
+    "furnace_types_steep/balance_T0/lambert": (0.9997, 0.00242, 0.0070, 0.0275),
+    "furnace_types_steep/balance_T0/normal": (1.0005, 0.00274, 0.0063, 0.0230),
+    "furnace_types_steep/balance_T0/mirror": (1.0005, 0.00236, 0.0064, 0.0264),
+    "furnace_types_steep/balance_T0/dielectric": (0.9991, 0.00336, 0.0078, 0.0357),
+    "furnace_types_steep/balance_T0/transparent": (0.9969, 0.00299, 0.0097, 0.0377),
+    "furnace_types_steep/pairwise_T1/lambert": (1.0008, 0.00334, 0.0035, 0.0133),
+    "furnace_types_steep/pairwise_T1/normal": (1.0000, 0.00368, 0.0033, 0.0137),
+    "furnace_types_steep/pairwise_T1/mirror": (0.9990, 0.00453, 0.0047, 0.0201),
+    "furnace_types_steep/pairwise_T1/dielectric": (0.9972, 0.00540, 0.0068, 0.0286),
+    "furnace_types_steep/pairwise_T1/transparent": (0.9959, 0.00492, 0.0067, 0.0228),
+    "furnace_types_grazing/mis/lambert": (1.0011, 0.00079, 0.0042, 0.0128),
+    "furnace_types_grazing/mis/normal": (1.0007, 0.00088, 0.0042, 0.0156),
+    "furnace_types_grazing/mis/mirror": (0.9998, 0.00081, 0.0044, 0.0152),
+    "furnace_types_grazing/mis/dielectric": (0.8434, 0.00217, 0.1554, 0.1860),
+    "furnace_types_grazing/mis/transparent": (1.0001, 0.00097, 0.0035, 0.0130),
+    "furnace_types_grazing/path_nogi/lambert": (1.0011, 0.00079, 0.0042, 0.0128),
+    "furnace_types_grazing/path_nogi/normal": (1.0007, 0.00088, 0.0042, 0.0156),
+    "furnace_types_grazing/path_nogi/mirror": (0.9998, 0.00081, 0.0044, 0.0152),
+    "furnace_types_grazing/path_nogi/dielectric": (0.8434, 0.00217, 0.1554, 0.1860),
+    "furnace_types_grazing/path_nogi/transparent": (1.0001, 0.00097, 0.0035, 0.0130),
+    "furnace_types_grazing/initial/lambert": (1.0005, 0.00313, 0.0124, 0.0455),
+    "furnace_types_grazing/initial/normal": (1.0017, 0.00463, 0.0159, 0.0623),
+    "furnace_types_grazing/initial/mirror": (1.0023, 0.00370, 0.0145, 0.0650),
+    "furnace_types_grazing/initial/dielectric": (1.0041, 0.00460, 0.0208, 0.0941),
+    "furnace_types_grazing/initial/transparent": (1.0001, 0.00515, 0.0192, 0.0763),
+    "furnace_types_grazing/balance_T0/lambert": (0.9996, 0.00309, 0.0066, 0.0320),
+    "furnace_types_grazing/balance_T0/normal": (1.0021, 0.00445, 0.0086, 0.0298),
+    "furnace_types_grazing/balance_T0/mirror": (1.0028, 0.00436, 0.0082, 0.0390),
+    "furnace_types_grazing/balance_T0/dielectric": (1.0051, 0.00493, 0.0111, 0.0504),
+    "furnace_types_grazing/balance_T0/transparent": (0.9997, 0.00561, 0.0116, 0.0508),
+    "furnace_types_grazing/pairwise_T1/lambert": (1.0015, 0.00453, 0.0048, 0.0240),
+    "furnace_types_grazing/pairwise_T1/normal": (1.0029, 0.00468, 0.0066, 0.0239),
+    "furnace_types_grazing/pairwise_T1/mirror": (0.9991, 0.00683, 0.0066, 0.0289),
+    "furnace_types_grazing/pairwise_T1/dielectric": (1.0049, 0.00948, 0.0095, 0.0427),
+    "furnace_types_grazing/pairwise_T1/transparent": (0.9989, 0.00712, 0.0078, 0.0319),
 }
 
 # Reference behaviour that is not the closed form ("Quirks reproduced"): asserted darker than the
@@ -482,7 +567,9 @@ MEASURED = {
 # DESIGN.md and not asserted: BRDF rays start at hitPoint + normalOffset * normal (pg/DirectMISIntegrator.cpp:106,
 # pg/ReSTIRIntegrator.cpp:139) while the cosines are taken from hitPoint, +0.05 % (steep) to +0.3 % (grazing, n = 64).
 QUIRKS = {("blocked", "constant_T0"), ("blocked", "constant_T1")} | {
-    (sc, est, strip) for sc in ("furnace_steep", "furnace_grazing") for est in ("mis", "path_nogi") for strip in KD_KS_STRIPS}
+    (sc, est, strip) for sc in ("furnace_steep", "furnace_grazing") for est in ("mis", "path_nogi") for strip in KD_KS_STRIPS} | {
+    # the same quirk on the DIELECTRIC strip, which MIS and the path tracer sample and evaluate as Phong (kd and ks, n = 8)
+    (sc, est, "dielectric") for sc in ("furnace_types_steep", "furnace_types_grazing") for est in ("mis", "path_nogi")}
 
 
 def is_quirk(scene, estimator, region):

@@ -1,0 +1,374 @@
+"""Scenes, cases and shared oracle renders for the material tests (tests/test_materials_oracle.py on the CPU oracle,
+tests/test_gpu_materials.py on the HIP renderer).  TEST INFRASTRUCTURE ONLY.
+
+The renderer takes seven material classes (pg/enums.h:3-11) and branches on them in three places: the BRDF eval
+(Phong for PHONG and DIELECTRIC, Lambert otherwise), the BRDF sampling (cosine for LAMBERT alone, the Phong mixture
+for every other class) and the G-buffer's 1/I_M (PHONG and DIELECTRIC).  That makes three classes of identical
+behaviour for the ReSTIR passes -- CLASSES -- two when no BRDF candidate is drawn (CLASSES_NO_BRDF), and two for the
+MIS and path ground truths, which sample by the eval's rule (rs_mis.h).
+
+  zoo()          a Cornell-like room in which every one of the seven classes covers >= 100 pixels at 64 x 48
+  edge_room()    a room whose floor, back wall and left wall are LAMBERT, PHONG and MIRROR -- one wall per class --
+                 and which has two emitter materials; EDGES changes one property of those walls or of one emitter
+  rough_scene()  scenes.textured_cornell with the Phong block's roughness map replaced (ROUGH_MAPS)
+
+Comparisons.  Frames are sanitised and hold no NaN: np.array_equal.  G-buffers and reservoirs hold what the scene
+gave them -- a NaN shininess, a NaN weight sum -- and a NaN equals nothing, itself included, so `same` is
+np.array_equal with equal_nan=True: every element equal, or NaN on both sides.
+"""
+from __future__ import annotations
+
+import copy
+import functools
+from dataclasses import replace
+
+import numpy as np
+
+from restir_amd import params as P
+from restir_amd import scenes
+from restir_amd.scenes import (DIELECTRIC, DIELECTRIC_TRANSPARENT, LAMBERT, MIRROR, NORMAL, PHONG, UNSUPPORTED,
+                               Material)
+
+SIZES = ((64, 48), (50, 38))          # 50 x 38 is no multiple of the 8 x 8 wave tile
+TYPE_COL, IM_COL, SHIN_COL = 17, 18, 15
+ALL_TYPES = (NORMAL, LAMBERT, PHONG, MIRROR, DIELECTRIC, DIELECTRIC_TRANSPARENT, UNSUPPORTED)
+MIN_PIXELS = 100
+
+CLASSES = ((NORMAL, MIRROR, DIELECTRIC_TRANSPARENT, UNSUPPORTED), (LAMBERT,), (PHONG, DIELECTRIC))
+CLASSES_NO_BRDF = ((NORMAL, LAMBERT, MIRROR, DIELECTRIC_TRANSPARENT, UNSUPPORTED), (PHONG, DIELECTRIC))
+CLASSES_MIS = CLASSES_NO_BRDF         # rs_mis.h, rs_path.h: Phong for {2, 4}, Lambert for the rest
+# m_brdf -> re-typings (every material of the first type becomes the second) that cross a class boundary
+CROSSINGS = {2: ((NORMAL, LAMBERT), (LAMBERT, PHONG), (DIELECTRIC, MIRROR)), 0: ((MIRROR, PHONG), (DIELECTRIC, NORMAL))}   # (the LAMBERT wall has ks = 0: Phong's eval of it is Lambert's)
+
+
+def rotation(classes):
+    """type -> the next type of its class (cyclic): every material of a class of more than one member is re-typed,
+    none leaves its class"""
+    return {t: c[(i + 1) % len(c)] for c in classes for i, t in enumerate(c)}
+
+
+def same(a, b):
+    return np.array_equal(a, b, equal_nan=True)
+
+
+# ---------------------------------------------------------------- rooms
+SURFACES = ("floor", "ceiling", "back", "left", "right", "tall", "short")
+LIGHT_A = Material(le=(17.0, 12.0, 4.0), type=LAMBERT)
+LIGHT_B = Material(le=(6.0, 9.0, 14.0), type=LAMBERT)
+
+ZOO = {
+    "floor": Material(kd=(0.73, 0.73, 0.73), type=LAMBERT),
+    "ceiling": Material(kd=(0.6, 0.6, 0.55), ks=(0.2, 0.25, 0.3), shininess=6.0, type=NORMAL),
+    "back": Material(kd=(0.3, 0.35, 0.4), ks=(0.5, 0.45, 0.4), shininess=24.0, type=MIRROR),
+    "left": Material(kd=(0.65, 0.05, 0.05), ks=(0.15, 0.3, 0.3), shininess=3.0, type=DIELECTRIC_TRANSPARENT),
+    "right": Material(kd=(0.12, 0.45, 0.15), ks=(0.3, 0.1, 0.2), shininess=12.0, type=UNSUPPORTED),
+    "tall": Material(kd=(0.55, 0.55, 0.55), ks=(0.04, 0.04, 0.04), shininess=64.0, type=PHONG),
+    "short": Material(kd=(0.4, 0.35, 0.3), ks=(0.3, 0.3, 0.35), shininess=9.0, type=DIELECTRIC),
+}
+EDGE_ROOM = {
+    "floor": Material(kd=(0.73, 0.73, 0.73), type=LAMBERT),
+    "ceiling": Material(kd=(0.7, 0.7, 0.7), type=LAMBERT),
+    "back": Material(kd=(0.4, 0.4, 0.45), ks=(0.3, 0.3, 0.25), shininess=16.0, type=PHONG),
+    "left": Material(kd=(0.65, 0.05, 0.05), ks=(0.2, 0.2, 0.2), shininess=8.0, type=MIRROR),
+    "right": Material(kd=(0.12, 0.45, 0.15), type=LAMBERT),
+    "tall": Material(kd=(0.55, 0.55, 0.55), ks=(0.04, 0.04, 0.04), shininess=64.0, type=PHONG),
+    "short": Material(kd=(0.5, 0.5, 0.4), ks=(0.2, 0.2, 0.2), shininess=4.0, type=NORMAL),
+}
+EDGE_WALLS = ("floor", "back", "left")          # LAMBERT, PHONG, MIRROR: one wall per class
+
+
+def room(materials, light_a=LIGHT_A, light_b=LIGHT_B, name="room"):
+    """The Cornell shell of scenes._cornell_shell with one material per surface (SURFACES order, then the two emitter
+    materials): four ceiling quads of light_a, and of light_b one ceiling quad and one quad on the back wall."""
+    b = scenes._Builder()
+    m = {k: b.material(replace(materials[k])) for k in SURFACES}
+    b.quad([-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0], m["floor"], normal=[0, 0, 1])
+    b.quad([-1, -1, 2], [-1, 1, 2], [1, 1, 2], [1, -1, 2], m["ceiling"], normal=[0, 0, -1])
+    b.quad([-1, 1, 0], [1, 1, 0], [1, 1, 2], [-1, 1, 2], m["back"], normal=[0, -1, 0])
+    b.quad([-1, -1, 0], [-1, 1, 0], [-1, 1, 2], [-1, -1, 2], m["left"], normal=[1, 0, 0])
+    b.quad([1, 1, 0], [1, -1, 0], [1, -1, 2], [1, 1, 2], m["right"], normal=[-1, 0, 0])
+    b.box([-0.65, 0.0, 0.0], [-0.05, 0.6, 1.2], m["tall"], rot_z=0.3)
+    b.box([0.05, -0.55, 0.0], [0.65, 0.05, 0.6], m["short"], rot_z=-0.3)
+    la, lb = b.material(replace(light_a)), b.material(replace(light_b))
+    h, z = 0.09, 1.98
+    for cx, cy in ((-0.5, -0.4), (0.5, -0.4), (-0.5, 0.5), (0.5, 0.5)):
+        b.quad([cx - h, cy - h, z], [cx - h, cy + h, z], [cx + h, cy + h, z], [cx + h, cy - h, z], la, normal=[0, 0, -1])
+    b.quad([-h, -h, z], [-h, h, z], [h, h, z], [h, -h, z], lb, normal=[0, 0, -1])
+    y, cx, cz = 0.985, 0.45, 1.45
+    b.quad([cx + h, y, cz - h], [cx - h, y, cz - h], [cx - h, y, cz + h], [cx + h, y, cz + h], lb, normal=[0, -1, 0])
+    return b.build(scenes.CORNELL_CAMERA, name)
+
+
+def zoo():
+    return room(ZOO, name="zoo")
+
+
+def edge_room():
+    return room(EDGE_ROOM, name="edge_room")
+
+
+def retyped(sc, mapping):
+    """a copy of `sc` with every material's type sent through `mapping` (types it does not name stay)"""
+    out = copy.copy(sc)
+    out.materials = [replace(m, type=mapping.get(m.type, m.type)) for m in sc.materials]
+    return out
+
+
+def camera(sc, f):
+    return scenes.orbit_camera(sc.camera, f, 24, 0.3)
+
+
+# ---------------------------------------------------------------- configurations
+def reuse_params(mis="pairwise", **kw):
+    base = dict(m_area=3, m_brdf=2, do_temporal=1, do_visibility_pass=1, do_spatial=1, spatial_neighbors=4,
+                spatial_passes=2, spatial_mis=mis)
+    base.update(kw)
+    return P.default_params(**base)
+
+
+INITIAL = {"a3b2": dict(m_area=3, m_brdf=2), "a0b1": dict(m_area=0, m_brdf=1)}
+REUSE = {m: dict(mis=m) for m in ("constant", "debias_contrib", "debias_z", "balance", "pairwise")}
+REUSE["balance_reject"] = dict(mis="balance", reject_dissimilar=1)
+
+
+def config(name):
+    return P.default_params(**INITIAL[name]) if name in INITIAL else reuse_params(**REUSE[name])
+
+
+def edge_params():
+    """the pairwise temporal + spatial configuration of the value-edge cases"""
+    return P.default_params(m_area=3, m_brdf=2, do_temporal=1, do_spatial=1, spatial_neighbors=4, spatial_mis="pairwise")
+
+
+EDGE_SIZE, EDGE_FRAMES, ZOO_FRAMES = (50, 38), 2, 3
+MIS_SPP, PATH_SPP, PATH_BOUNCES = 4, 2, 3
+
+# ---------------------------------------------------------------- value edges
+_KS = (0.2, 0.2, 0.2)
+
+
+def _walls(**kw):
+    return lambda mats, la, lb: ({k: replace(v, **kw) if k in EDGE_WALLS else v for k, v in mats.items()}, la, lb)
+
+
+def _floor(**kw):
+    return lambda mats, la, lb: ({k: replace(v, **kw) if k == "floor" else v for k, v in mats.items()}, la, lb)
+
+
+def _light_b(**kw):
+    return lambda mats, la, lb: (mats, la, replace(lb, **kw))
+
+
+EDGES = {
+    # shininess: a = (n + 1) / 2 pi and pow(cos, n) of the lobe pdf, 1/I_M, the lobe sampling's 1 / (n + 1)
+    "shin_0": _walls(shininess=0.0),
+    "shin_1": _walls(shininess=1.0),
+    "shin_1e4": _walls(shininess=1e4),
+    "shin_1e6": _walls(shininess=1e6),
+    "shin_inf": _walls(shininess=float("inf")),
+    "shin_nan": _walls(shininess=float("nan")),
+    "shin_neg_ks0": _walls(shininess=-0.5, ks=(0.0, 0.0, 0.0)),      # pow(0, n < 0) = inf times (1 - pf) = 0: NaN
+    "shin_neg_ks": _walls(shininess=-0.5, ks=_KS),
+    "kd0": _walls(kd=(0.0, 0.0, 0.0), ks=(0.3, 0.4, 0.5)),           # pf = 0
+    "kd0_ks0": _walls(kd=(0.0, 0.0, 0.0), ks=(0.0, 0.0, 0.0)),       # pf = 0 / 0
+    "ks_1p5": _walls(ks=(1.5, 1.5, 1.5)),
+    "lambert_ks": _floor(ks=(0.3, 0.3, 0.3), shininess=8.0),         # a lobe in the pdf that the eval ignores
+    # emitters
+    "emitter_phong": _light_b(kd=(0.5, 0.5, 0.5), ks=(0.3, 0.3, 0.3), shininess=16.0, type=PHONG),
+    "le_green": _light_b(le=(0.0, 12.0, 0.0)),
+    "le_negative_red": _light_b(le=(-1.0, 12.0, 0.0)),               # the sum is positive: emissive
+    "le_1e-30": _light_b(le=(1e-30, 1e-30, 1e-30)),
+    "le_1e30": _light_b(le=(1e30, 1e30, 1e30)),
+}
+
+
+def edge_scene(case=None):
+    if case is None:
+        return edge_room()
+    mats, la, lb = EDGES[case](dict(EDGE_ROOM), LIGHT_A, LIGHT_B)
+    return room(mats, la, lb, name=f"edge_{case}")
+
+
+# ---------------------------------------------------------------- roughness maps (shininess = 2 / r^2 - 2 per pixel)
+def _rough_zero_blocks():
+    yy, xx = np.mgrid[0:16, 0:24]
+    r = (60 + 5 * xx + 3 * yy).astype(np.uint8)
+    r[(xx % 8 < 4) & (yy % 8 < 4)] = 0                              # 4 x 4 blocks of r = 0: shininess = +inf
+    return r[:, :, None]
+
+
+def _rough_ones():
+    yy, xx = np.mgrid[0:16, 0:24]
+    r = (90 + 4 * xx + 5 * yy).astype(np.uint8)
+    r[(xx % 6 < 3) & (yy % 4 < 2)] = 255                            # r = 1: shininess = 0
+    return r[:, :, None]
+
+
+def _rough_float():
+    yy, xx = np.mgrid[0:16, 0:24]
+    r = (0.3 + 0.02 * xx + 0.01 * yy).astype(np.float32)
+    r[(xx % 8 < 4) & (yy % 8 < 4)] = 1.5                            # shininess = 2 / 2.25 - 2 < 0
+    r[(xx % 8 >= 4) & (yy % 8 >= 4)] = 0.0                          # shininess = +inf
+    return np.repeat(r[:, :, None], 3, axis=2)
+
+
+ROUGH_MAPS = {"u8_zero_blocks": _rough_zero_blocks, "u8_255": _rough_ones, "float_1p5_and_0": _rough_float}
+
+
+def rough_scene(which=None):
+    """textured_cornell (8-bit random roughness in [40, 200) on the Phong block) with that map replaced"""
+    sc = scenes.textured_cornell()
+    if which is not None:
+        tex = list(sc.textures)
+        tex[sc.materials[3].shininess_map - 1] = scenes.Texture(ROUGH_MAPS[which](), 0)
+        sc.textures = tex
+        sc.name = f"rough_{which}"
+    return sc
+
+
+# ---------------------------------------------------------------- OBJ default: an MTL without Pc and without Ns
+OBJ_KD = {"floor": (0.8, 0.8, 0.75), "ceiling": (0.7, 0.7, 0.7), "back": (0.5, 0.6, 0.7), "left": (0.8, 0.2, 0.2),
+          "right": (0.3, 0.7, 0.35), "tall": (0.75, 0.75, 0.75), "short": (0.6, 0.5, 0.03)}
+OBJ_KS = (0.5, 0.4, 0.02)                                             # 0.02: the linear branch of the expansion
+
+
+def srgb_expand(u):
+    """Utils::expand (pg/utils.cpp:209-218) in float32, the power through the shared rs_libm.h"""
+    import oracle_lib
+    u = np.float32(u)
+    if u <= 0:
+        return 0.0
+    if u >= 1:
+        return 1.0
+    if u <= np.float32(0.04045):
+        return float(u / np.float32(12.92))
+    x = (u + np.float32(0.055)) / np.float32(1.055)
+    return float(oracle_lib.libm_f2("powf", [x], [np.float32(2.4)])[0])
+
+
+def obj_default_scene():
+    """the array scene the default MTL must load as: type NORMAL, shininess 0, Kd and Ks sRGB-expanded, Ke as written"""
+    mats = {k: Material(kd=tuple(srgb_expand(c) for c in OBJ_KD[k]), ks=tuple(srgb_expand(c) for c in OBJ_KS),
+                        shininess=0.0, type=NORMAL) for k in SURFACES}
+    return room(mats, replace(LIGHT_A, type=NORMAL, shininess=0.0), replace(LIGHT_B, type=NORMAL, shininess=0.0),
+                name="obj_default")
+
+
+def write_default_obj(sc, obj_path):
+    """`sc`'s geometry as OBJ with an MTL that has Kd, Ks and (on the emitters) Ke only: no Pc, no Ns"""
+    import os
+    mtl = os.path.splitext(obj_path)[0] + ".mtl"
+    kd = [OBJ_KD[k] for k in SURFACES]
+    with open(mtl, "w") as f:
+        for i, m in enumerate(sc.materials):
+            f.write(f"newmtl m{i}\n")
+            if i < len(kd):
+                f.write(f"Kd {' '.join(f'{c:.9g}' for c in kd[i])}\nKs {' '.join(f'{c:.9g}' for c in OBJ_KS)}\n")
+            else:
+                f.write(f"Ke {' '.join(f'{c:.9g}' for c in m.le)}\n")
+    pos = np.asarray(sc.positions, np.float32).reshape(-1, 3)
+    nrm = np.asarray(sc.normals, np.float32).reshape(-1, 3)
+    with open(obj_path, "w") as f:
+        f.write(f"mtllib {os.path.basename(mtl)}\n")
+        f.write("".join(f"v {x:.9g} {y:.9g} {z:.9g}\n" for x, y, z in pos))
+        f.write("".join(f"vn {x:.9g} {y:.9g} {z:.9g}\n" for x, y, z in nrm))
+        cur = -1
+        for t in range(sc.n_tris):
+            if sc.tri_material[t] != cur:
+                cur = int(sc.tri_material[t])
+                f.write(f"usemtl m{cur}\n")
+            b = 3 * t + 1
+            f.write(f"f {b}//{b} {b + 1}//{b + 1} {b + 2}//{b + 2}\n")
+
+
+# ---------------------------------------------------------------- the oracle's renders, computed once and shared
+class Render:
+    """frames (list of (H, W, 3)), the G-buffer and the reservoirs after the last frame; read-only"""
+
+    def __init__(self, frames, gbuffer, reservoirs):
+        self.frames, self.gbuffer, self.reservoirs = frames, gbuffer, reservoirs
+        for a in (*frames, gbuffer, reservoirs):
+            a.setflags(write=False)
+
+
+def run_restir(renderer, handle, sc, n_frames, frame_fn):
+    """n_frames over the orbit camera on either renderer; frame_fn(handle, camera, f) renders one frame"""
+    renderer.reset_history()
+    frames = [np.array(frame_fn(handle, camera(sc, f), f), copy=True) for f in range(n_frames)]
+    return Render(frames, np.array(renderer.gbuffer(), copy=True), np.array(renderer.reservoirs(), copy=True))
+
+
+def oracle_restir(sc, prm, size, n_frames):
+    import oracle_lib as O
+    o, os_ = O.OracleRenderer(*size), O.OracleScene(sc)
+    return run_restir(o, os_, sc, n_frames, lambda h, c, f: o.render(h, c, prm, f))
+
+
+def gpu_restir(sc, prm, size, n_frames, traversal=None, split=None):
+    from restir_amd.renderer import Renderer
+    g = Renderer(*size)
+    if traversal:
+        g.set_traversal(traversal)
+    if split:
+        g.set_initial_split(split)
+    gs = g.load_scene(sc)
+    return run_restir(g, gs, sc, n_frames, lambda h, c, f: g.produce_restir(h, c, prm, f))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_zoo(cfg, size):
+    return oracle_restir(zoo(), config(cfg), size, ZOO_FRAMES)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_edge(case):
+    return oracle_restir(edge_scene(case), edge_params(), EDGE_SIZE, EDGE_FRAMES)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_rough(which):
+    return oracle_restir(rough_scene(which), edge_params(), EDGE_SIZE, EDGE_FRAMES)
+
+
+def oracle_mis(sc, size, n_frames=2):
+    import oracle_lib as O
+    o, os_ = O.OracleRenderer(*size), O.OracleScene(sc)
+    return [o.render_direct_mis(os_, sc.camera, P.default_params(), f, MIS_SPP) for f in range(n_frames)]
+
+
+def oracle_path(sc, size, n_frames=2):
+    import oracle_lib as O
+    import path_oracle as PO
+    o, os_ = O.OracleRenderer(*size), O.OracleScene(sc)
+    return [PO.render_path(o, os_, sc.camera, P.default_params(), f, PATH_SPP, max_bounces=PATH_BOUNCES)
+            for f in range(n_frames)]
+
+
+def _differ(a, b):
+    return ~((a == b) | (np.isnan(a) & np.isnan(b)))
+
+
+def assert_same_render(a, b, what, type_column=True):
+    """frames, G-buffer (without the type column if asked) and reservoirs equal element by element; the message
+    names every part that is not"""
+    bad = []
+    for f, (x, y) in enumerate(zip(a.frames, b.frames)):
+        if not np.array_equal(x, y):
+            bad.append(f"frame {f}: {int(np.any(x != y, -1).sum())} pixels")
+    ga, gb = a.gbuffer, b.gbuffer
+    if not type_column:
+        keep = [c for c in range(ga.shape[-1]) if c != TYPE_COL]
+        ga, gb = ga[..., keep], gb[..., keep]
+    if not same(ga, gb):
+        d = _differ(ga, gb)
+        bad.append(f"G-buffer: columns {sorted(set(np.nonzero(d)[-1].tolist()))} on {int(d.any(-1).sum())} pixels")
+    if not same(a.reservoirs, b.reservoirs):
+        d = _differ(a.reservoirs, b.reservoirs)
+        bad.append(f"reservoirs: columns {sorted(set(np.nonzero(d)[-1].tolist()))} on {int(d.any(-1).sum())} pixels")
+    assert not bad, f"{what}: " + "; ".join(bad)
+
+
+def type_pixels(gbuffer):
+    """pixels per material type among the G-buffer's hits"""
+    hit = gbuffer[..., 16] > 0
+    return {t: int((hit & (gbuffer[..., TYPE_COL] == t)).sum()) for t in ALL_TYPES}

@@ -59,7 +59,7 @@ def _reference(backend, name):
     return _refs[name]
 
 
-@pytest.mark.parametrize("name", ["open", "blocked", "furnace_steep", "furnace_grazing"])
+@pytest.mark.parametrize("name", ["open", "blocked", *CF.FURNACE_SCENES])
 def test_scene_is_valid(backend, name):
     """closed_form.validate: no emitter behind another, none below a receiver's horizon, none with a shading normal
     off its plane; the regions the assertions sum over are populated (every furnace strip covers >= 100 pixels)."""
@@ -117,7 +117,7 @@ def test_polygon_formula_known_values():
 
 
 CASES = [(s, e) for s in ("open", "blocked") for e in CF.ESTIMATORS] + \
-        [(s, e) for s in ("furnace_steep", "furnace_grazing") for e in CF.FURNACE_ESTIMATORS]
+        [(s, e) for s in CF.FURNACE_SCENES for e in CF.FURNACE_ESTIMATORS]
 
 
 @pytest.mark.parametrize("scene,estimator", CASES, ids=[f"{s}-{e}" for s, e in CASES])
@@ -128,3 +128,14 @@ def test_estimator_against_closed_form(backend, scene, estimator):
     CF.check(scene, estimator, CF.measure(backend, cf, ref, estimator))
     n = 4 if CF.ESTIMATORS[estimator][0] == "restir" else 8
     assert np.array_equal(backend.mean_image(cf, estimator, CF.SEEDS[0], n), backend.mean_image(cf, estimator, CF.SEEDS[0], n))
+
+
+@pytest.mark.parametrize("scene", ["furnace_types_steep", "furnace_types_grazing"])
+@pytest.mark.parametrize("estimator", ["mis", "path_nogi"])
+def test_dielectric_strip_is_phong_to_mis_and_path(backend, scene, estimator):
+    """The kd + ks darkness of the DIELECTRIC strip is Phong's quirk and nothing else: with that strip typed PHONG the
+    image is the same bit for bit (and the quirk itself is bracketed by test_estimator_against_closed_form)."""
+    a = backend.mean_image(CF.get_scene(scene), estimator, CF.SEEDS[0], 8)
+    b = backend.mean_image(CF.get_scene(scene + "_swapped"), estimator, CF.SEEDS[0], 8)
+    assert np.array_equal(a, b) and a.max() > 0
+    assert CF.is_quirk(scene, estimator, "dielectric") and not CF.is_quirk(scene, estimator, "normal")

@@ -67,7 +67,7 @@ def _reference(name):
     return _refs[name]
 
 
-@pytest.mark.parametrize("name", ["open", "blocked", "furnace_steep", "furnace_grazing"])
+@pytest.mark.parametrize("name", ["open", "blocked", *CF.FURNACE_SCENES])
 def test_scene_is_valid_at_the_gpu_gbuffer(name):
     cf, ref = CF.get_scene(name), _reference(name)
     counts = CF.validate(cf, ref.x, ref.n)
@@ -81,7 +81,7 @@ def test_scene_is_valid_at_the_gpu_gbuffer(name):
 
 
 CASES = [(s, e) for s in ("open", "blocked") for e in CF.ESTIMATORS] + \
-        [(s, e) for s in ("furnace_steep", "furnace_grazing") for e in CF.FURNACE_ESTIMATORS]
+        [(s, e) for s in CF.FURNACE_SCENES for e in CF.FURNACE_ESTIMATORS]
 
 
 def _run(scene, estimator, traversal=None):
@@ -106,3 +106,13 @@ def test_estimator_against_closed_form(scene, estimator):
 def test_blocked_scene_under_pinned_traversal(traversal):
     """The shadow edge under each walk kind: spatial + temporal reuse with pairwise weights."""
     _run("blocked", "pairwise_T1", traversal)
+
+
+@pytest.mark.parametrize("scene", ["furnace_types_steep", "furnace_types_grazing"])
+@pytest.mark.parametrize("estimator", ["mis", "path_nogi"])
+def test_dielectric_strip_is_phong_to_mis_and_path(scene, estimator):
+    """tests/test_closed_form_oracle.py's check on the renderer: the DIELECTRIC strip typed PHONG, the same image"""
+    b = _backend()
+    x = b.mean_image(CF.get_scene(scene), estimator, CF.SEEDS[0], 8)
+    y = b.mean_image(CF.get_scene(scene + "_swapped"), estimator, CF.SEEDS[0], 8)
+    assert np.array_equal(x, y) and x.max() > 0
