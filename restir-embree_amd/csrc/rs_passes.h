@@ -533,6 +533,23 @@ struct FrameSlot {
     }
 };
 
+// Area candidate c of a pixel (initialRenderPass :246-266) from its pick: the sample and its unoccluded evaluation
+// (returned: L, the shadow ray and its need), and the candidate's RIS weight m * p-hat * W when it is lit (wu) and
+// when it is not (wo: unlit_weight).  Call: the pow core by call, not inlined.
+template <bool Call = false>
+__device__ __forceinline__ FPre area_candidate(const DevScene& S, const FrameConst& F, vec3 pos, const ShadeFrame& sf,
+                                               Rng& rng, int c, uint32_t pick, bool tv, bool alive, float inv_ma,
+                                               float& wu, float& wo) {
+    float Wc, mis;
+    rng.n = cand_slot(c) + 1u;                          // slot +0 was the pick (area_pick)
+    const Sample s = area_sample_at<Call>(S, F, pos, sf, rng, pick, Wc, mis);
+    const FPre p = evaluate_f_pre<Call>(F, s, pos, false, sf, tv, alive);
+    const float ph = length(p.L);
+    const float m = F.m_brdf > 0 ? mis : inv_ma;
+    wu = m * ph * Wc;
+    wo = unlit_weight(m, p, Wc);
+    return p;
+}
 // One batch of area candidates [c0, c0 + kB) (initialRenderPass :246-266): sample, unoccluded f, one
 // walk for the batch's shadow rays; returns each candidate's RIS weight w in w_out.  Only two weights per
 // candidate stay live across the walk -- the unoccluded one and the unlit one (unlit_weight) -- instead
@@ -549,14 +566,7 @@ __device__ __forceinline__ void area_batch(const DevScene& S, const FrameConst& 
     const float inv_ma = 1.0f / (float)F.m_area;
 #pragma unroll
     for (int k = 0; k < kB; ++k) {
-        float Wc, mis;
-        rng.n = cand_slot(c0 + k) + 1u;                 // slot +0 was the pick (area_pick)
-        const Sample s = area_sample_at(S, F, pos, sf, rng, pick[k], Wc, mis);
-        const FPre p = evaluate_f_pre(F, s, pos, false, sf, tv, alive && c0 + k < c_end);
-        const float ph = length(p.L);
-        const float m = F.m_brdf > 0 ? mis : inv_ma;
-        wu[k] = m * ph * Wc;
-        wo[k] = unlit_weight(m, p, Wc);
+        const FPre p = area_candidate(S, F, pos, sf, rng, c0 + k, pick[k], tv, alive && c0 + k < c_end, inv_ma, wu[k], wo[k]);
         act[k] = p.need; okb[k] = p.ok; dir[k] = p.dir; tf[k] = p.tfar; occ[k] = false;
         rays += act[k] ? 1u : 0u;
     }
@@ -581,14 +591,7 @@ __device__ __forceinline__ void area_batch_px(const DevScene& S, const FrameCons
     const float inv_ma = 1.0f / (float)F.m_area;
 #pragma unroll
     for (int k = 0; k < kA; ++k) {
-        float Wc, mis;
-        rng.n = cand_slot(c0 + k) + 1u;                 // slot +0 was the pick (area_pick)
-        const Sample s = area_sample_at(S, F, pos, sf, rng, pick[k], Wc, mis);
-        const FPre p = evaluate_f_pre(F, s, pos, false, sf, tv, alive && c0 + k < c_end);
-        const float ph = length(p.L);
-        const float m = F.m_brdf > 0 ? mis : inv_ma;
-        wu[k] = m * ph * Wc;
-        wo[k] = unlit_weight(m, p, Wc);
+        const FPre p = area_candidate(S, F, pos, sf, rng, c0 + k, pick[k], tv, alive && c0 + k < c_end, inv_ma, wu[k], wo[k]);
         need |= p.need ? 1u << k : 0u;
         ok |= p.ok ? 1u << k : 0u;
         dir[k] = p.dir; tf[k] = p.tfar;
@@ -606,20 +609,40 @@ __device__ __forceinline__ void area_batch_px(const DevScene& S, const FrameCons
     for (int k = 0; k < kA; ++k) w_out[k] = ((lit >> k) & 1u) ? wu[k] : wo[k];   // evaluate_f_post
     ride_occ = (occ >> kA) & 1u;
 }
-// the selected area candidate's sample and (unoccluded) f, re-drawn from its RNG slots (the pick through the
-// same table source L as the first draw's)
+// the selected area candidate c into the reservoir: its sample and (unoccluded) f, re-drawn from its RNG slots (the
+// pick through the same table source L as the first draw's), and its p-hat
 template <class LT>
-__device__ __forceinline__ Sample area_redraw(const LT& L, const DevScene& S, const FrameConst& F, vec3 pos,
-                                             const ShadeFrame& sf, Rng& rng, int c, bool tv, vec3& f) {
+__device__ __forceinline__ void area_redraw(const LT& L, const DevScene& S, const FrameConst& F, vec3 pos,
+                                           const ShadeFrame& sf, Rng& rng, int c, bool tv, Res& r, vec3& f, float& phat) {
     float Wc, mis;
     rng.n = cand_slot(c);
     const Sample s = area_sample(L, S, F, pos, sf, rng, Wc, mis);
     f = evaluate_f_pre(F, s, pos, false, sf, tv, true).L;
-    return s;
+    phat = length(f);
+    r.p = s.p; r.n = s.n; r.li = s.li;
 }
-__device__ __forceinline__ Sample area_redraw(const DevScene& S, const FrameConst& F, vec3 pos, const ShadeFrame& sf,
-                                             Rng& rng, int c, bool tv, vec3& f) {
-    return area_redraw(LightGlobal(S), S, F, pos, sf, rng, c, tv, f);
+// a batch's weights w[0..kN) of candidates c0.. (below c_end) into the reservoir, in candidate order (addSample's
+// draw is the candidate's slot +3); sel: the last candidate taken
+template <int kN>
+__device__ __forceinline__ void add_weights(Res& r, Rng& rng, const float* w, int c0, int c_end, bool alive, int& sel) {
+#pragma unroll
+    for (int k = 0; k < kN; ++k) {
+        if (c0 + k < c_end) {
+            rng.n = cand_slot(c0 + k) + 3u;
+            if (alive && res_add_w(r, w[k], 0, rng)) sel = c0 + k;
+        }
+    }
+}
+// The initial pass's end (:288-297).  Every candidate adds confidence 1 (Reservoir::addSample, pg/Reservoir.h:35):
+// counted here, not carried through the candidate loops (one register less across every shadow walk).  The final
+// p-hat (:289) equals the selected candidate's (same arguments), so it is not re-evaluated.  A pixel that is not
+// alive leaves an empty reservoir.
+__device__ __forceinline__ void finish_initial(Res& r, bool alive, float best_phat, vec3& f_sel, const FrameConst& F) {
+    if (!alive) { f_sel = mk(0, 0, 0); r = res_empty(); return; }
+    r.conf = F.m_area + F.m_brdf;
+    const float ph = smp_valid(smp_of(r)) ? best_phat : 0.0f;
+    r.W = ph > 0.0f ? 1.0f / ph * r.wsum : 0.0f;
+    res_cap(r, F.cap);
 }
 
 // initialRenderPass (pg/ReSTIRIntegrator.cpp:236-298) for the lanes with `in_pass`.  f_sel returns the
@@ -663,8 +686,7 @@ __device__ __forceinline__ Res initial_ris(const LT& L, const DevScene& S, const
                 float w;
                 pick[0] = area_pick(L, S, rng, c);
                 area_batch_px<T, 1, 0>(S, F, pos, fs.load(), rng, c, F.m_area, alive, tv, pick, &w, rays, no_ride, ride_occ);
-                rng.n = cand_slot(c) + 3u;
-                if (alive && res_add_w(r, w, 0, rng)) sel = c;
+                add_weights<1>(r, rng, &w, c, F.m_area, alive, sel);
             }
         }
         for (int c0 = 0; (kLane || tv) && c0 < a_loop; c0 += kB) {
@@ -678,13 +700,7 @@ __device__ __forceinline__ Res initial_ris(const LT& L, const DevScene& S, const
 #pragma unroll
                 for (int k = 0; k < kB; ++k) pick[k] = next[k];
             }
-#pragma unroll
-            for (int k = 0; k < kB; ++k) {
-                if (c0 + k < F.m_area) {
-                    rng.n = cand_slot(c0 + k) + 3u;
-                    if (alive && res_add_w(r, w[k], 0, rng)) sel = c0 + k;
-                }
-            }
+            add_weights<kB>(r, rng, w, c0, F.m_area, alive, sel);
         }
         if constexpr (!kLane) {
             if (ride) {
@@ -701,31 +717,17 @@ __device__ __forceinline__ Res initial_ris(const LT& L, const DevScene& S, const
                     for (int k = 0; k < kB - 1; ++k) pick[k] = area_pick(L, S, rng, a_loop + k);
                 }
                 area_batch_px<T, kB - 1, 1>(S, F, pos, sf, rng, a_loop, F.m_area, alive, tv, pick, w, rays, p, ride_occ);
-#pragma unroll
-                for (int k = 0; k < kB - 1; ++k) {
-                    if (a_loop + k < F.m_area) {
-                        rng.n = cand_slot(a_loop + k) + 3u;
-                        if (alive && res_add_w(r, w[k], 0, rng)) sel = a_loop + k;
-                    }
-                }
-                if (sel >= 0) {
-                    const Sample sa = area_redraw(L, S, F, pos, fs.load(), rng, sel, tv, f_sel);
-                    best_phat = length(f_sel);
-                    r.p = sa.p; r.n = sa.n; r.li = sa.li;
-                }
+                add_weights<kB - 1>(r, rng, w, a_loop, F.m_area, alive, sel);
+                if (sel >= 0) area_redraw(L, S, F, pos, fs.load(), rng, sel, tv, r, f_sel, best_phat);
                 const vec3 f = evaluate_f_post(p, ride_occ);
                 const float ph = length(f);
                 rng.n = cand_slot(F.m_area) + 3u;
                 if (alive && res_add(r, s, mis * ph * Wc, 0, rng)) { best_phat = ph; f_sel = f; }
             } else if (sel >= 0) {
-                const Sample s = area_redraw(L, S, F, pos, fs.load(), rng, sel, tv, f_sel);
-                best_phat = length(f_sel);
-                r.p = s.p; r.n = s.n; r.li = s.li;
+                area_redraw(L, S, F, pos, fs.load(), rng, sel, tv, r, f_sel, best_phat);
             }
         } else if (sel >= 0) {
-            const Sample s = area_redraw(L, S, F, pos, fs.load(), rng, sel, tv, f_sel);
-            best_phat = length(f_sel);
-            r.p = s.p; r.n = s.n; r.li = s.li;
+            area_redraw(L, S, F, pos, fs.load(), rng, sel, tv, r, f_sel, best_phat);
         }
     }
     if (F.m_brdf > 0) {
@@ -742,13 +744,7 @@ __device__ __forceinline__ Res initial_ris(const LT& L, const DevScene& S, const
             if (alive && res_add(r, s, w, 0, rng)) { best_phat = ph; f_sel = f; }
         }
     }
-    if (!alive) { f_sel = mk(0, 0, 0); return res_empty(); }
-    // every candidate adds confidence 1 (Reservoir::addSample, pg/Reservoir.h:35): counted here, not
-    // carried through the candidate loops (one register less across every shadow walk)
-    r.conf = F.m_area + F.m_brdf;
-    float ph = smp_valid(smp_of(r)) ? best_phat : 0.0f;
-    r.W = ph > 0.0f ? 1.0f / ph * r.wsum : 0.0f;
-    res_cap(r, F.cap);
+    finish_initial(r, alive, best_phat, f_sel, F);
     return r;
 }
 
@@ -905,6 +901,19 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
+// The sorted passes' bucket counts cur[64] (lane = bucket) to offsets in place: a 64-lane exclusive scan.  Returns
+// the number of rays.  The caller puts a wave_lds_sync() in front and behind.
+__device__ __forceinline__ uint32_t bucket_offsets(uint32_t* cur, int lane) {
+    const uint32_t cnt = cur[lane];
+    uint32_t incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t v = __shfl_up(incl, o);
+        incl += lane >= o ? v : 0u;
+    }
+    cur[lane] = incl - cnt;
+    return __shfl(incl, 63);
+}
 // the pixel index of lane `l` of this thread's wave tile (pixel_of's layout, unclamped)
 __device__ __forceinline__ uint32_t tile_pixel(const FrameConst& F, int ya, int yb, int l) {
     int bx, by;
@@ -929,14 +938,9 @@ __device__ __forceinline__ AreaCand area_cand(const DevScene& S, const FrameCons
                                               Rng& rng, int c, bool tv, bool alive, float inv_ma) {
     AreaCand a;
     a.pick = area_pick(S, rng, c);
-    float Wc, mis;
-    rng.n = cand_slot(c) + 1u;
-    const Sample s = area_sample_at<true>(S, F, pos, sf, rng, a.pick, Wc, mis);
-    const FPre pr = evaluate_f_pre<true>(F, s, pos, false, sf, tv, alive);
+    float wo;                                   // +-0 (the same reservoir update) or NaN
+    const FPre pr = area_candidate<true>(S, F, pos, sf, rng, c, a.pick, tv, alive, inv_ma, a.wu, wo);
     a.bucket = ray_bucket(S, a.pick, pr.dir);
-    const float m = F.m_brdf > 0 ? mis : inv_ma;
-    a.wu = m * length(pr.L) * Wc;
-    const float wo = unlit_weight(m, pr, Wc);   // +-0 (the same reservoir update) or NaN
     a.wo_nan = wo != wo;
     a.ok = pr.ok;
     a.need = pr.need;
@@ -1012,15 +1016,7 @@ __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst&
                     }
                 }
                 wave_lds_sync();
-                const uint32_t cnt = L.cur[lane];                       // lane = bucket: exclusive scan
-                uint32_t incl = cnt;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const uint32_t v = __shfl_up(incl, o);
-                    incl += lane >= o ? v : 0u;
-                }
-                const uint32_t n_rays = __shfl(incl, 63);
-                L.cur[lane] = incl - cnt;
+                const uint32_t n_rays = bucket_offsets(L.cur, lane);
                 wave_lds_sync();
 #pragma unroll
                 for (int k = 0; k < kSortChunk; ++k)
@@ -1071,9 +1067,7 @@ __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst&
             }
             if (sel >= 0) {
                 const GElem g = G.load(p);
-                const Sample s = area_redraw(S, F, g.pos, make_frame(g, cam), rng, sel, tv, f_sel);
-                best_phat = length(f_sel);
-                r.p = s.p; r.n = s.n; r.li = s.li;
+                area_redraw(LightGlobal(S), S, F, g.pos, make_frame(g, cam), rng, sel, tv, r, f_sel, best_phat);
             }
         }
         if (F.m_brdf > 0) {
@@ -1104,15 +1098,7 @@ __device__ __forceinline__ void sorted_tile(const DevScene& S, const FrameConst&
                 if (alive && res_add(r, s, w, 0, rng)) { best_phat = ph; f_sel = f; }
             }
         }
-        if (alive) {                                                    // as initial_ris's epilogue
-            r.conf = F.m_area + F.m_brdf;
-            const float ph = smp_valid(smp_of(r)) ? best_phat : 0.0f;
-            r.W = ph > 0.0f ? 1.0f / ph * r.wsum : 0.0f;
-            res_cap(r, F.cap);
-        } else {
-            r = res_empty();
-            f_sel = mk(0, 0, 0);
-        }
+        finish_initial(r, alive, best_phat, f_sel, F);
     }
     if (ris) {
         Rw.store(p, r);
@@ -1288,16 +1274,12 @@ __global__ void __launch_bounds__(64 * kSplit, RS_WAVES(T, RS_INITIAL_WAVES, RS_
         int sel = -1;
         for (int c = 0; c < A; ++c) {
             rng.n = cand_slot(c) + 3u;
-            if (alive && res_add_w(r, L.w[c * 64 + lane], 1, rng)) sel = c;
+            if (alive && res_add_w(r, L.w[c * 64 + lane], 0, rng)) sel = c;
         }
-        if (sel >= 0) {                                                 // re-draw the selected area sample
-            const Sample s = area_redraw(S, F, pos, fs.load(), rng, sel, tv, f_sel);
-            best_phat = length(f_sel);
-            r.p = s.p; r.n = s.n; r.li = s.li;
-        }
+        if (sel >= 0) area_redraw(LightGlobal(S), S, F, pos, fs.load(), rng, sel, tv, r, f_sel, best_phat);
         for (int c = A; c < n; ++c) {
             rng.n = cand_slot(c) + 3u;
-            if (alive && res_add_w(r, L.w[c * 64 + lane], 1, rng)) {
+            if (alive && res_add_w(r, L.w[c * 64 + lane], 0, rng)) {
                 const float4* q = L.brdf + (c - A) * 3 * 64;
                 const float4 a = q[lane], b = q[64 + lane], d = q[128 + lane];
                 r.p = xyz(a); r.n = xyz(b); r.li = xyz(d);
@@ -1306,12 +1288,7 @@ __global__ void __launch_bounds__(64 * kSplit, RS_WAVES(T, RS_INITIAL_WAVES, RS_
             }
         }
     }
-    if (!alive) { f_sel = mk(0, 0, 0); r = res_empty(); }
-    else {
-        const float ph = smp_valid(smp_of(r)) ? best_phat : 0.0f;
-        r.W = ph > 0.0f ? 1.0f / ph * r.wsum : 0.0f;
-        res_cap(r, F.cap);
-    }
+    finish_initial(r, alive, best_phat, f_sel, F);
     if (ris) {
         Rw.store(p, r);
         if (fuse_shade) store_rgb(fb, p, shade_px(r, f_sel, le));
@@ -1494,15 +1471,7 @@ __global__ void __launch_bounds__(256, RS_WAVES(T, RS_TEMPORAL_WAVES, RS_TEMPORA
                     bk |= b << (8 * k);
                 }
             wave_lds_sync();
-            const uint32_t cnt_b = L.cur[lane];
-            uint32_t incl = cnt_b;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const uint32_t v = __shfl_up(incl, o);
-                incl += lane >= o ? v : 0u;
-            }
-            const uint32_t n_rays = __shfl(incl, 63);
-            L.cur[lane] = incl - cnt_b;
+            const uint32_t n_rays = bucket_offsets(L.cur, lane);
             wave_lds_sync();
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -1623,6 +1592,50 @@ __device__ __forceinline__ size_t list_px(const FrameConst& F, const Rng& rng, u
 // neighbour-list cache entries per thread in LDS (list positions 1..k; k <= kNbrCache - 1)
 constexpr int kNbrCache = 17;
 
+// The steps k_spatial and k_spatial_sorted share.
+// An emissive pixel keeps its reservoir (:319-324).
+__device__ __forceinline__ void spatial_emissive(const ResBuf& Rr, const ResBuf& Rw, float* fb, int fuse_shade, size_t p,
+                                                 vec3 le) {
+    Res r = Rr.load(p);
+    Rw.store(p, r);
+    if (fuse_shade) store_rgb(fb, p, shade_px(r, mk(0, 0, 0), le));
+}
+// Neighbour selection (:334-374) of the pixel with G element `th`: accept(i, q) takes draw i's pixel q when it passes,
+// in draw order.
+template <class AcceptF>
+__device__ __forceinline__ void select_neighbors(const FrameConst& F, const GBuf& G, const GElem& th, const Rng& rng,
+                                                 int x, int y, AcceptF accept) {
+    for (int i = 0; i < F.k; ++i) {
+        size_t q = neighbor_px(F, rng, i, x, y);
+        if (any_pos(G.le(q))) continue;
+        if (F.reject) {
+            float4 nq = G.g1[q];
+            float ns = dot(xyz(nq), th.nrm);
+            if (ns < F.min_normal_sim) continue;
+            float nd = G.g0[q].w;
+            float dr = 0;
+            if (nd > 0) dr = th.depth / nd;
+            float hd = F.max_depth_diff * 0.5f;
+            if (dr < 1.0f - hd || dr > 1.0f + hd) continue;
+        }
+        accept(i, q);
+    }
+}
+// The pass's end once W is final: the cap, the store and the fused shade.
+__device__ __forceinline__ void spatial_store(const FrameConst& F, const ResBuf& Rw, float* fb, int fuse_shade, size_t p,
+                                              bool alive, Res& res, vec3 f_sel, vec3 le) {
+    res_cap(res, F.cap);
+    if (alive) {
+        Rw.store(p, res);
+        if (fuse_shade) store_rgb(fb, p, shade_px(res, f_sel, le));
+    }
+}
+// W of the modes without a correction factor (CONSTANT, BALANCE, PAIRWISE), from the selected sample's p-hat (:481)
+__device__ __forceinline__ void spatial_w(Res& res, vec3 f_sel) {
+    const float fph = smp_valid(smp_of(res)) ? length(f_sel) : 0.0f;
+    res.W = fph > 0.0f ? res.wsum / fph : 0.0f;
+}
+
 // spatialReusePass (pg/ReSTIRIntegrator.cpp:316-542); shade fused when this is the last pass.
 // List loops run to the uniform bound k+1 with `i < cnt` as a predicate (convergent ray queries).
 // CM = 1: the CONSTANT-MIS instantiation (the metric point), compiled without the other modes' code
@@ -1641,35 +1654,19 @@ k_spatial(DevScene S, FrameConst F, GBuf G, ResBuf Rr, ResBuf Rw, int pass_idx, 
     GElem th = G.load(p);
     const bool emissive = any_pos(th.le);
     const bool alive = in && !emissive;
-    if (in && emissive) {                                  // :319-324
-        Res r = Rr.load(p);
-        Rw.store(p, r);
-        if (fuse_shade) store_rgb(fb, p, shade_px(r, mk(0, 0, 0), th.le));
-    }
+    if (in && emissive) spatial_emissive(Rr, Rw, fb, fuse_shade, p, th.le);
     if (__ballot(alive) != 0) {
         Rng rng; rng.init(F.seed, F.frame, PASS_SPATIAL0 + (uint32_t)pass_idx, (uint32_t)p);
-        // neighbour selection (:334-374); the accepted list is cached in LDS when k <= kNbrCache - 1
-        // (list position i -> pixel), otherwise list_px re-derives it from the RNG slots
+        // the accepted list is cached in LDS when k <= kNbrCache - 1 (list position i -> pixel), otherwise
+        // list_px re-derives it from the RNG slots
         const bool cached = F.k < kNbrCache;
         uint64_t acc = 0;
         int M = 1;
-        for (int i = 0; i < F.k; ++i) {
-            size_t q = neighbor_px(F, rng, i, x, y);
-            if (any_pos(G.le(q))) continue;
-            if (F.reject) {
-                float4 nq = G.g1[q];
-                float ns = dot(xyz(nq), th.nrm);
-                if (ns < F.min_normal_sim) continue;
-                float nd = G.g0[q].w;
-                float dr = 0;
-                if (nd > 0) dr = th.depth / nd;
-                float hd = F.max_depth_diff * 0.5f;
-                if (dr < 1.0f - hd || dr > 1.0f + hd) continue;
-            }
+        select_neighbors(F, G, th, rng, x, y, [&](int i, size_t q) {
             acc |= 1ull << i;
             if (cached) nbr[M * 256 + threadIdx.x] = (uint32_t)q;
             M += 1;
-        }
+        });
         auto list_q = [&](int i) -> size_t {
             if (!cached) return list_px(F, rng, acc, i, x, y, p);
             return (i == 0 || i >= M) ? p : (size_t)nbr[i * 256 + threadIdx.x];
@@ -1782,42 +1779,40 @@ k_spatial(DevScene S, FrameConst F, GBuf G, ResBuf Rr, ResBuf Rw, int pass_idx, 
             float rw = mis * rph * ri.W;
             if (li && res_add(res, si, rw, ri.conf, rng)) { sel = i; f_sel = f; }
         }
-        float fph = smp_valid(smp_of(res)) ? length(f_sel) : 0.0f;  // :481
         if (mode == MIS_CONSTANT || mode == MIS_BALANCE || mode == MIS_PAIRWISE) {
-            res.W = fph > 0.0f ? res.wsum / fph : 0.0f;
-        } else if (mode == MIS_DEBIAS_Z) {                // :494-506
-            int Z = 0;
-            float corr = 1.0f;
-            for (int i = 0; i < kk; ++i) {
-                const bool li = alive && i < cnt;
-                size_t qi = list_q(i);
-                bool occ = occluded<T>(S, F, li, G.pos(qi), res.p, rays);
-                if (li && !occ) Z += 1;
-            }
-            if (Z > 0 && M > 0) corr = (1.0f / (float)Z) / rcpM;
-            res.W = fph > 0.0f ? corr * res.wsum / fph : 0.0f;
-        } else if (mode == MIS_DEBIAS_CONTRIB) {          // :515-538
-            Sample ss = smp_of(Rr.load(list_q(sel)));
-            float num = 0, den = 0, cw = 0, corr = 0;
-            for (int i = 0; i < kk; ++i) {
-                const bool li = alive && i < cnt;
-                size_t qi = list_q(i);
-                int ci = __float_as_int(Rr.r[3 * qi + 2].w);
-                float ph = length(evaluate_f<T>(S, F, ss, cam, G.load(qi), true, li, rays));
-                if (li) {
-                    den += ph * (float)ci;
-                    if (i == sel) num = ph * (float)ci;
+            spatial_w(res, f_sel);
+        } else {
+            float fph = smp_valid(smp_of(res)) ? length(f_sel) : 0.0f;  // :481
+            if (mode == MIS_DEBIAS_Z) {                       // :494-506
+                int Z = 0;
+                float corr = 1.0f;
+                for (int i = 0; i < kk; ++i) {
+                    const bool li = alive && i < cnt;
+                    size_t qi = list_q(i);
+                    bool occ = occluded<T>(S, F, li, G.pos(qi), res.p, rays);
+                    if (li && !occ) Z += 1;
                 }
+                if (Z > 0 && M > 0) corr = (1.0f / (float)Z) / rcpM;
+                res.W = fph > 0.0f ? corr * res.wsum / fph : 0.0f;
+            } else if (mode == MIS_DEBIAS_CONTRIB) {          // :515-538
+                Sample ss = smp_of(Rr.load(list_q(sel)));
+                float num = 0, den = 0, cw = 0, corr = 0;
+                for (int i = 0; i < kk; ++i) {
+                    const bool li = alive && i < cnt;
+                    size_t qi = list_q(i);
+                    int ci = __float_as_int(Rr.r[3 * qi + 2].w);
+                    float ph = length(evaluate_f<T>(S, F, ss, cam, G.load(qi), true, li, rays));
+                    if (li) {
+                        den += ph * (float)ci;
+                        if (i == sel) num = ph * (float)ci;
+                    }
+                }
+                if (den > 0) cw = num / den;
+                if (M > 0) corr = cw / rcpM;
+                res.W = fph > 0.0f ? corr * res.wsum / fph : 0.0f;
             }
-            if (den > 0) cw = num / den;
-            if (M > 0) corr = cw / rcpM;
-            res.W = fph > 0.0f ? corr * res.wsum / fph : 0.0f;
         }
-        res_cap(res, F.cap);
-        if (alive) {
-            Rw.store(p, res);
-            if (fuse_shade) store_rgb(fb, p, shade_px(res, f_sel, th.le));
-        }
+        spatial_store(F, Rw, fb, fuse_shade, p, alive, res, f_sel, th.le);
     }
     count_rays(C, rays, 0, t0, y);
 }
@@ -1857,30 +1852,14 @@ k_spatial_sorted(DevScene S, FrameConst F, GBuf G, ResBuf Rr, ResBuf Rw, int pas
     GElem th = G.load(p);
     const bool emissive = any_pos(th.le);
     const bool alive = in && !emissive;
-    if (in && emissive) {                                  // :319-324
-        Res r = Rr.load(p);
-        Rw.store(p, r);
-        if (fuse_shade) store_rgb(fb, p, shade_px(r, mk(0, 0, 0), th.le));
-    }
+    if (in && emissive) spatial_emissive(Rr, Rw, fb, fuse_shade, p, th.le);
     if (__ballot(alive) != 0) {
         Rng rng; rng.init(F.seed, F.frame, PASS_SPATIAL0 + (uint32_t)pass_idx, (uint32_t)p);
-        int M = 1;                                          // neighbour selection (:334-374), as k_spatial
-        for (int i = 0; i < F.k; ++i) {
-            size_t q = neighbor_px(F, rng, i, x, y);
-            if (any_pos(G.le(q))) continue;
-            if (F.reject) {
-                float4 nq = G.g1[q];
-                float ns = dot(xyz(nq), th.nrm);
-                if (ns < F.min_normal_sim) continue;
-                float nd = G.g0[q].w;
-                float dr = 0;
-                if (nd > 0) dr = th.depth / nd;
-                float hd = F.max_depth_diff * 0.5f;
-                if (dr < 1.0f - hd || dr > 1.0f + hd) continue;
-            }
+        int M = 1;
+        select_neighbors(F, G, th, rng, x, y, [&](int, size_t q) {
             nbr[(M - 1) * 256 + threadIdx.x] = (uint32_t)q;
             M += 1;
-        }
+        });
         rng.n = 2u * (uint32_t)F.k;
         const int cnt = M, kk = F.k + 1;
         auto list_q = [&](int i) -> size_t { return (i == 0 || i >= M) ? p : (size_t)nbr[(i - 1) * 256 + threadIdx.x]; };
@@ -1901,15 +1880,7 @@ k_spatial_sorted(DevScene S, FrameConst F, GBuf G, ResBuf Rr, ResBuf Rw, int pas
             }
         }
         wave_lds_sync();
-        const uint32_t cnt_b = L.cur[lane];
-        uint32_t incl = cnt_b;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t v = __shfl_up(incl, o);
-            incl += lane >= o ? v : 0u;
-        }
-        const uint32_t n_rays = __shfl(incl, 63);
-        L.cur[lane] = incl - cnt_b;
+        const uint32_t n_rays = bucket_offsets(L.cur, lane);
         wave_lds_sync();
 #pragma unroll
         for (int i = 0; i < kSpatialSortMax; ++i)
@@ -1973,13 +1944,8 @@ k_spatial_sorted(DevScene S, FrameConst F, GBuf G, ResBuf Rr, ResBuf Rw, int pas
             const float rw = rcpM * length(f) * rr.W;
             if (alive && i < cnt && res_add(res, smp_of(rr), rw, rr.conf, rng)) f_sel = f;
         }
-        const float fph = smp_valid(smp_of(res)) ? length(f_sel) : 0.0f;  // :481
-        res.W = fph > 0.0f ? res.wsum / fph : 0.0f;
-        res_cap(res, F.cap);
-        if (alive) {
-            Rw.store(p, res);
-            if (fuse_shade) store_rgb(fb, p, shade_px(res, f_sel, th.le));
-        }
+        spatial_w(res, f_sel);
+        spatial_store(F, Rw, fb, fuse_shade, p, alive, res, f_sel, th.le);
     }
     count_rays(C, rays, 0, t0, y);
 }
