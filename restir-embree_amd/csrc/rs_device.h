@@ -237,20 +237,54 @@ __device__ __forceinline__ bool is_phong(int type) { return type == MT_PHONG || 
 // (Measured, DESIGN.md section 5: a flag computed once per pixel in make_frame costs the initial pass registers.)
 // (Call: the pow's core as a called function, rs_libm.h rs_powf_sel -- for the register-bound per-lane kernels)
 constexpr uint32_t kLobeSkipMax = 0x4cbebc20u;          // the bits of 1e8f
+__device__ __forceinline__ bool pdf_lobe(const ShadeFrame& s) {
+    return s.omp != 0.0f || __float_as_uint(s.shin) > kLobeSkipMax;
+}
+// The lobe's power on one direction for both of its users.  The pdf's base is max(0, d) and the BRDF's max(d, 0)
+// (gmax(x, y) = x < y ? y : x), d = dot(wi, wr): the same bits unless d is NaN (+0 against NaN) or -0 (+0 against -0).
+// A caller with both on one wi pays the pow once: the first power is on the pdf's base where the pdf takes one,
+// else on the BRDF's; the BRDF's own power is taken only where both are wanted and the bits differ -- such a base
+// is -0 or NaN, which rs_powf_sel answers from its special cases (RS_LM_POW_EDGE: no second core) -- and is skipped
+// by the whole wave otherwise.
+// A pixel that wants neither takes no pow, so what is said above of Lambert surfaces holds.
+struct LobePow { float pdf, brdf; };
+__device__ __forceinline__ float pdf_base(const ShadeFrame& s, vec3 wi) { return gmax(0.0f, dot(wi, s.wr)); }
+__device__ __forceinline__ float brdf_base(const ShadeFrame& s, vec3 wi) { return gmax(dot(wi, s.wr), 0.0f); }
+template <bool Call = false>
+__device__ __forceinline__ LobePow lobe_pow(const ShadeFrame& s, vec3 wi) {
+    const bool lobe = pdf_lobe(s), ph = is_phong(s.type);
+    const float bp = pdf_base(s, wi), bb = brdf_base(s, wi);
+    LobePow r{0.0f, 0.0f};
+    if (lobe || ph) r.pdf = r.brdf = rs_powf_sel(lobe ? bp : bb, s.shin, Call);
+    const bool own = lobe && ph && __float_as_uint(bp) != __float_as_uint(bb);
+    if (__ballot(own) != 0) {
+        if (own) r.brdf = rs_powf_sel(bb, s.shin, RS_LM_POW_EDGE);
+    }
+    return r;
+}
+__device__ __forceinline__ float phong_pdf(const ShadeFrame& s, vec3 wi, const LobePow& lp) {
+    float pdf = gmax(dot(s.nrm, wi), 0.0f) * kOneOverPi * s.pf;
+    pdf += pdf_lobe(s) ? s.a * lp.pdf * s.omp : 0.0f;
+    return pdf;
+}
 template <bool Call = false>
 __device__ __forceinline__ float phong_pdf(const ShadeFrame& s, vec3 wi) {
     float pdf = gmax(dot(s.nrm, wi), 0.0f) * kOneOverPi * s.pf;
-    const bool lobe = s.omp != 0.0f || __float_as_uint(s.shin) > kLobeSkipMax;
-    pdf += lobe ? s.a * rs_powf_sel(gmax(0.0f, dot(wi, s.wr)), s.shin, Call) * s.omp : 0.0f;
+    pdf += pdf_lobe(s) ? s.a * rs_powf_sel(pdf_base(s, wi), s.shin, Call) * s.omp : 0.0f;
     return pdf;
 }
 // BRDF eval dispatch (pg/ReSTIRIntegrator.h:32-41): Phong for PHONG/DIELECTRIC
 // (pg/MaterialPhong.cpp:122-148, with the cached 1/I_M), Lambert otherwise (pg/MaterialLambert.cpp:33-41)
+__device__ __forceinline__ vec3 eval_brdf(const ShadeFrame& s, const LobePow& lp) {
+    vec3 f = s.kd_pi;
+    if (!is_phong(s.type)) return f;
+    return f + s.ks_im * lp.brdf;
+}
 template <bool Call = false>
 __device__ __forceinline__ vec3 eval_brdf(const ShadeFrame& s, vec3 wi) {
     vec3 f = s.kd_pi;
     if (!is_phong(s.type)) return f;
-    float pw = rs_powf_sel(gmax(dot(wi, s.wr), 0.0f), s.shin, Call);
+    float pw = rs_powf_sel(brdf_base(s, wi), s.shin, Call);
     return f + s.ks_im * pw;
 }
 __device__ __forceinline__ float phong_pdf(const GElem& g, vec3 cam, vec3 wi) { return phong_pdf(make_frame(g, cam), wi); }

@@ -260,6 +260,9 @@ static const double rs_lm_exp2_tab_host[128] = RS_LM_EXP2_TAB_INIT;
 #define RS_LM_LN2_128_LO 1.4907929134926466e-12
 #define RS_LM_128_OVER_LN2 184.6649652337873
 
+#if defined(__HIP_DEVICE_COMPILE__)
+__attribute__((always_inline))      /* where it is not to be inlined, rs_lm_pow_core_call is the callee */
+#endif
 RS_LM double rs_lm_pow_core(float ax, float y) {
     uint32_t b = rs_lm_fbits(ax);
     int e = -127;
@@ -301,19 +304,23 @@ __host__ __device__ static __attribute__((noinline)) double rs_lm_pow_core_call(
     return rs_lm_pow_core(ax, y);
 }
 #endif
-/* x^y (C99 special cases); call != 0 (a constant at every call site): the core by rs_lm_pow_core_call */
+/* x^y (C99 special cases).  call, a constant at every call site, says how the device takes the core: 0 inlined,
+   1 by rs_lm_pow_core_call, RS_LM_POW_EDGE not at all -- the caller knows x to be a zero or a NaN, which the
+   special cases answer (a base that would need the core gives NaN).  The host ignores it. */
+#define RS_LM_POW_EDGE (-1)
 RS_LM float rs_powf_sel(float x, float y, int call) {
     if (y == 0.0f || x == 1.0f) return 1.0f;
     if (x != x || y != y) return x + y;
-    const double ay = y < 0.0f ? -(double)y : (double)y;
-    const int y_inf = ay > 3.4028234663852886e38;
-    /* y an odd integer: |y| < 2^24 and y == trunc(y) and trunc(y) odd */
+    const float ay = y < 0.0f ? -y : y;
+    const int y_inf = rs_lm_fbits(ay) == 0x7f800000u;
+    /* y an odd integer: |y| < 2^24 and y == trunc(y) and trunc(y) odd (below 2^24 both conversions are exact
+       in 32 bits: one instruction each on the device, where the 64-bit ones are a dozen) */
     int y_odd = 0, y_int = 0;
     if (!y_inf) {
-        if (ay >= 16777216.0) { y_int = 1; }
+        if (ay >= 16777216.0f) { y_int = 1; }
         else {
-            const int64_t iy = (int64_t)ay;
-            y_int = (double)iy == ay;
+            const int32_t iy = (int32_t)ay;
+            y_int = (float)iy == ay;
             y_odd = y_int && (iy & 1);
         }
     }
@@ -329,7 +336,7 @@ RS_LM float rs_powf_sel(float x, float y, int call) {
     else if (x < 0.0f && !y_int) return RS_LM_FNAN;
     else {
 #if defined(__HIP_DEVICE_COMPILE__)
-        r = (float)(call ? rs_lm_pow_core_call(ax, y) : rs_lm_pow_core(ax, y));
+        r = call < 0 ? RS_LM_FNAN : (float)(call ? rs_lm_pow_core_call(ax, y) : rs_lm_pow_core(ax, y));
 #else
         (void)call;
         r = (float)rs_lm_pow_core(ax, y);

@@ -28,21 +28,34 @@ __device__ __forceinline__ float mis_power(float pdf, float other) {
 }
 __device__ __forceinline__ vec3 dvs(vec3 v, float s) { return mk(v.x / s, v.y / s, v.z / s); }   // glm vec3 / scalar
 __device__ __forceinline__ float cos_pdf(vec3 n, vec3 wi) { return gmax(dot(n, wi), 0.0f) * kOneOverPi; }
-__device__ __forceinline__ float lobe_pdf(vec3 wi, vec3 wr, float g) {      // pg/Distribution.h:65-67
-    return (g + 1.0f) * kOneOver2Pi * rs_powf(gmax(0.0f, dot(wi, wr)), g);
+// The lobe's power on wi for the pdf (base max(0, d)) and for the BRDF (base max(d, 0)), as rs_device.h lobe_pow:
+// one pow where the two bases are the same bits, the BRDF's own only where they are not (d NaN or -0: no core)
+__device__ __forceinline__ LobePow mis_lobe_pow(const MisSurf& h, vec3 wi) {
+    LobePow r{0.0f, 0.0f};
+    if (!h.phong) return r;
+    const float bp = gmax(0.0f, dot(wi, h.wr)), bb = gmax(dot(wi, h.wr), 0.0f);
+    r.pdf = r.brdf = rs_powf(bp, h.shin);
+    const bool own = __float_as_uint(bp) != __float_as_uint(bb);
+    if (__ballot(own) != 0) {
+        if (own) r.brdf = rs_powf_sel(bb, h.shin, RS_LM_POW_EDGE);
+    }
+    return r;
+}
+__device__ __forceinline__ float lobe_pdf(float g, float pw) {              // pg/Distribution.h:65-67
+    return (g + 1.0f) * kOneOver2Pi * pw;
 }
 // getPdfForSample (pg/MaterialLambert.cpp:20-23, pg/MaterialPhong.cpp:94-119)
-__device__ __forceinline__ float mis_pdf_for(const MisSurf& h, vec3 wi) {
+__device__ __forceinline__ float mis_pdf_for(const MisSurf& h, vec3 wi, const LobePow& lp) {
     if (!h.phong) return cos_pdf(h.n, wi);
     float pdf = cos_pdf(h.n, wi) * h.pf;
-    pdf += lobe_pdf(wi, h.wr, h.shin) * (1.0f - h.pf);
+    pdf += lobe_pdf(h.shin, lp.pdf) * (1.0f - h.pf);
     return pdf;
 }
 // evaluateBRDF (pg/MaterialLambert.cpp:25-31, pg/MaterialPhong.cpp:69-92)
-__device__ __forceinline__ vec3 mis_brdf(const MisSurf& h, vec3 wi) {
+__device__ __forceinline__ vec3 mis_brdf(const MisSurf& h, const LobePow& lp) {
     vec3 f = h.kd * kOneOverPi;
     if (!h.phong) return f;
-    return f + (h.ks * h.i_m) * rs_powf(gmax(dot(wi, h.wr), 0.0f), h.shin);
+    return f + (h.ks * h.i_m) * lp.brdf;
 }
 // evaluateLightingGI (pg/MaterialLambert.cpp:10-18, pg/MaterialPhong.cpp:18-67)
 __device__ __forceinline__ vec3 mis_sample(const MisSurf& h, Rng& rng, vec3& f_r, float& pdf) {
@@ -54,15 +67,14 @@ __device__ __forceinline__ vec3 mis_sample(const MisSurf& h, Rng& rng, vec3& f_r
     }
     float r0 = rng.range(0.0f, h.maxD + h.maxS);
     vec3 wi;
-    if (r0 < h.maxD) {
-        wi = cosine_sample(h.n, rng);
-        f_r = h.kd * kOneOverPi;
-    } else {
-        wi = lobe_sample(h.wr, h.shin, rng);
-        f_r = (h.ks * h.i_m) * rs_powf(gmax(dot(wi, h.wr), 0.0f), h.shin);
-    }
+    const bool diffuse = r0 < h.maxD;
+    if (diffuse) wi = cosine_sample(h.n, rng);
+    else wi = lobe_sample(h.wr, h.shin, rng);
+    const LobePow lp = mis_lobe_pow(h, wi);
+    if (diffuse) f_r = h.kd * kOneOverPi;
+    else f_r = (h.ks * h.i_m) * lp.brdf;
     float pd = cos_pdf(h.n, wi) * h.pf;
-    float ps = lobe_pdf(wi, h.wr, h.shin) * (1.0f - h.pf);
+    float ps = lobe_pdf(h.shin, lp.pdf) * (1.0f - h.pf);
     pdf = pd + ps;
     if (dot(h.n, wi) < 0) f_r = mk(0, 0, 0);
     return wi;
@@ -117,11 +129,12 @@ __device__ __forceinline__ vec3 mis_light_part(const DevScene& S, const FrameCon
     const bool ok = alive && light_pdf != 0.0f && r_sqr != 0.0f && cI > 0 && cY > 0;
     const bool occ = occluded<T>(S, F, ok, h.pos, pt, rays);
     if (!ok || occ) return mk(0, 0, 0);
-    float pba = mis_pdf_for(h, ld) * amf;
+    const LobePow lp = mis_lobe_pow(h, ld);
+    float pba = mis_pdf_for(h, ld, lp) * amf;
     float w = mis_power(light_pdf, pba);
     if (!(w > 0.0f)) return mk(0, 0, 0);
     float G = cI * cY / r_sqr;
-    return dvs(((E.le * w) * mis_brdf(h, ld)) * G, light_pdf);
+    return dvs(((E.le * w) * mis_brdf(h, lp)) * G, light_pdf);
 }
 
 template <int T>

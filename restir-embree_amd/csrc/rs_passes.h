@@ -225,10 +225,12 @@ __device__ __forceinline__ bool occluded(const DevScene& S, const FrameConst& F,
 // Split in two around the shadow ray so callers can batch several rays into one traversal:
 // evaluate_f_pre computes the unoccluded L and the testOcclusion ray (dir = normalize(p - pos),
 // tfar = |p - pos| - tfarOffset, exactly as occluded<T>() forms them); evaluate_f_post applies V.
+// lp: the lobe's power on normalize(s.p - pos), where the caller already has it (lobe_pow); else it is taken here.
 struct FPre { vec3 L, dir; float tfar; bool ok, need; };
 template <bool Call = false>
 __device__ __forceinline__ FPre evaluate_f_pre(const FrameConst& F, const Sample& s, vec3 pos, bool emissive,
-                                               const ShadeFrame& sf, bool test_vis, bool alive) {
+                                               const ShadeFrame& sf, bool test_vis, bool alive,
+                                               const LobePow* lp = nullptr) {
     FPre r;
     r.ok = alive && smp_valid(s) && !emissive;
     vec3 ld = s.p - pos;
@@ -237,7 +239,7 @@ __device__ __forceinline__ FPre evaluate_f_pre(const FrameConst& F, const Sample
     float cI = gmax(dot(ld, sf.nrm), 0.0f);
     float cY = fabsf(dot(-ld, s.n));
     float G = cI * cY / r2;
-    r.L = (s.li * eval_brdf<Call>(sf, ld)) * G;
+    r.L = (s.li * (lp ? eval_brdf(sf, *lp) : eval_brdf<Call>(sf, ld))) * G;
     r.need = r.ok && test_vis && !(r.L.x == 0.0f && r.L.y == 0.0f && r.L.z == 0.0f);
     r.dir = ld;
     r.tfar = sqrtf(r2) - F.tfar_off;
@@ -449,9 +451,11 @@ __device__ __forceinline__ float emis_pdf_brdf(const DevScene& S, int id) { retu
 
 // areaSampleLight (pg/ReSTIRIntegrator.cpp:89-124), TriangleCDF::getTriangle (pg/TriangleCDF.cpp:36-54),
 // Sampling::sampleTriangle (pg/Sampling.cpp:63-76)
+// lp: the lobe's power on the direction to the sample, for the caller's evaluate_f_pre of it (the same
+// normalize(pt - pos) on the same operands, so the same bits)
 template <bool Call = false>
 __device__ __forceinline__ Sample area_sample_at(const DevScene& S, const FrameConst& F, vec3 pos, const ShadeFrame& sf,
-                                                 Rng& rng, uint32_t idx, float& W_out, float& mis_out) {
+                                                 Rng& rng, uint32_t idx, float& W_out, float& mis_out, LobePow& lp) {
     const EmisRec E = EmisRec::load(S.emis + 8 * idx);
     float r1 = rng.range(0, 1), r2 = rng.range(0, 1);
     float sr = sqrtf(r1);
@@ -464,16 +468,17 @@ __device__ __forceinline__ Sample area_sample_at(const DevScene& S, const FrameC
     ld = normalize(ld);
     float cY = gmax(dot(-ld, nn), 0.0f);
     float amf = cY / r2s;
-    float pba = phong_pdf<Call>(sf, ld) * amf;
+    lp = lobe_pow<Call>(sf, ld);
+    float pba = phong_pdf(sf, ld, lp) * amf;
     mis_out = m_area(F, pdf_area, pba);
     W_out = 1.0f / pdf_area;
     return Sample{pt, nn, E.le};
 }
 template <class LT>
 __device__ __forceinline__ Sample area_sample(const LT& L, const DevScene& S, const FrameConst& F, vec3 pos,
-                                              const ShadeFrame& sf, Rng& rng, float& W_out, float& mis_out) {
+                                              const ShadeFrame& sf, Rng& rng, float& W_out, float& mis_out, LobePow& lp) {
     const uint32_t idx = light_index(L, S.n_emis, rng.range(0.0f, 1.0f));
-    return area_sample_at(S, F, pos, sf, rng, idx, W_out, mis_out);
+    return area_sample_at(S, F, pos, sf, rng, idx, W_out, mis_out, lp);
 }
 
 // brdfSampleLight (pg/ReSTIRIntegrator.cpp:126-177)
@@ -542,8 +547,9 @@ __device__ __forceinline__ FPre area_candidate(const DevScene& S, const FrameCon
                                                float& wu, float& wo) {
     float Wc, mis;
     rng.n = cand_slot(c) + 1u;                          // slot +0 was the pick (area_pick)
-    const Sample s = area_sample_at<Call>(S, F, pos, sf, rng, pick, Wc, mis);
-    const FPre p = evaluate_f_pre<Call>(F, s, pos, false, sf, tv, alive);
+    LobePow lp;
+    const Sample s = area_sample_at<Call>(S, F, pos, sf, rng, pick, Wc, mis, lp);
+    const FPre p = evaluate_f_pre<Call>(F, s, pos, false, sf, tv, alive, &lp);
     const float ph = length(p.L);
     const float m = F.m_brdf > 0 ? mis : inv_ma;
     wu = m * ph * Wc;
@@ -616,8 +622,9 @@ __device__ __forceinline__ void area_redraw(const LT& L, const DevScene& S, cons
                                            const ShadeFrame& sf, Rng& rng, int c, bool tv, Res& r, vec3& f, float& phat) {
     float Wc, mis;
     rng.n = cand_slot(c);
-    const Sample s = area_sample(L, S, F, pos, sf, rng, Wc, mis);
-    f = evaluate_f_pre(F, s, pos, false, sf, tv, true).L;
+    LobePow lp;
+    const Sample s = area_sample(L, S, F, pos, sf, rng, Wc, mis, lp);
+    f = evaluate_f_pre(F, s, pos, false, sf, tv, true, &lp).L;
     phat = length(f);
     r.p = s.p; r.n = s.n; r.li = s.li;
 }
@@ -880,7 +887,7 @@ __global__ void __launch_bounds__(256, RS_WAVES(T, RS_INITIAL_WAVES, RS_INITIAL_
 constexpr int kSortChunk = RS_SORT_CHUNK;   // area candidates per sort round
 // Phase A's unoccluded candidate weights are kept for phase C in global memory (one coalesced 256-B store and load
 // per candidate and wave: FrameConst::cand_w) instead of phase C drawing every candidate again (its light pick, the
-// emitter record gathers, the sample, both Phong powf).  The region is the wave's hand-off slot: its resident wave
+// emitter record gathers, the sample, the Phong powf).  The region is the wave's hand-off slot: its resident wave
 // slot in the persistent launch (reused tile after tile, so the few MB stay in the caches), its 8x8 tile in a
 // one-launch grid (restir_capi.hip ensure_handoff sizes both by the launch)
 // ... and so are the needed shadow rays' (direction, tfar) for phase B (FrameConst::cand_ray: one 16-B load per ray
