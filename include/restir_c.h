@@ -539,6 +539,15 @@ int rs_debug_wide_tree(const rs_scene* scene, uint32_t* n_nodes, uint32_t* n_tri
  * for a pipelined rs_scene_update_positions and synchronises. */
 int rs_debug_bvh_tree(const rs_scene* scene, uint32_t* n_nodes, uint32_t* n_tris, float* nodes, int32_t* prims);
 
+/* ---- test hook: the scene's light tables (built on the device from the positions at creation, at every
+ * rs_scene_update_positions and at rs_scene_rebuild) ---------------------------------------------------------
+ * *n_emis = the number of emissive triangles.  With em != NULL (32 * *n_emis floats) it copies the scene's
+ * current emitter records -- per emitter eight float4: v0 | +-pdf_area (negative: the vertex normals differ),
+ * v1 | n0.x, v2 | n0.y, emission | n0.z, n1 | pick, n2 | pdf_brdf, (area, 1 / area, 0, 0), zeros --, with
+ * cdf != NULL (*n_emis floats) the light CDF and with guide != NULL (1025 int32) its guide table, guide[j] =
+ * lower_bound(cdf, j / 1024).  It waits for a pipelined rs_scene_update_positions and synchronises. */
+int rs_debug_light_tables(const rs_scene* scene, uint32_t* n_emis, float* em, float* cdf, int32_t* guide);
+
 #ifdef __cplusplus
 }
 #endif

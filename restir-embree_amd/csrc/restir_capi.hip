@@ -63,11 +63,9 @@ struct rs_scene {
     bool wide_on = false;
     float build_ms = 0.0f;
     float box_eps = 0.0f;                 // closest-hit box margin (rs_wide.h box_epsilon), set at the last full build
-    // host copies (rs_scene_rebuild re-derives the tables on the host)
-    std::vector<float> h_nrm;
-    std::vector<uint32_t> h_tri_mat;
-    std::vector<rs_material_desc> h_mats;
-    // rs_scene_update_positions: emissive triangle ids, refit plan, pinned upload ring (2 slots)
+    // emissive triangle ids in triangle order (set once at creation: the light tables' kernel reads the device
+    // copy, the emitter buckets the host one), refit plan, pinned upload ring (2 slots)
+    std::vector<uint32_t> emis_tri;
     int* d_emis_tri = nullptr;
     uint8_t* d_ebucket = nullptr;          // per emitter: its Morton bucket (the sorted initial pass's ray key)
     float ecen[3] = {0.0f, 0.0f, 0.0f};    // centre of the emitter centroids' bounds (the sorted spatial pass's key)
@@ -281,7 +279,6 @@ static inline hv3 hsub(hv3 a, hv3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z};
 static inline float hdot(hv3 a, hv3 b) { float x = a.x * b.x, y = a.y * b.y, z = a.z * b.z; return x + y + z; }
 static inline hv3 hcross(hv3 x, hv3 y) { return {x.y * y.z - y.y * x.z, x.z * y.x - y.z * x.x, x.x * y.y - y.x * x.y}; }
 static inline hv3 hnorm(hv3 a) { float s = 1.0f / std::sqrt(hdot(a, a)); return {a.x * s, a.y * s, a.z * s}; }
-static inline float hlen(hv3 a) { return std::sqrt(hdot(a, a)); }
 
 static void look_at_rh(hv3 eye, hv3 center, hv3 up, float m[4][4]) {
     hv3 f = hnorm(hsub(center, eye));
@@ -676,8 +673,8 @@ static int scene_from_arrays(rs_context* c, const std::vector<float>& pos, const
         tn[3 * t + 2] = make_float4(q[6], q[7], q[8], 0.0f);
     }
     rs_scene* s = new rs_scene();
-    s->ctx = c; s->n_tris = n; s->n_mats = n_mats;
-    s->h_nrm = nrm; s->h_tri_mat = tri_mat; s->h_mats.assign(mats, mats + n_mats);
+    s->ctx = c; s->n_tris = n; s->n_mats = n_mats; s->n_emis = (uint32_t)emis_tri.size();
+    s->emis_tri = std::move(emis_tri);
     auto bail = [&](int code, const std::string& m) { rs_scene_destroy(s); return fail(c, code, m); };
     std::string err;
     if (any_map) {
@@ -724,141 +721,56 @@ static int scene_from_arrays(rs_context* c, const std::vector<float>& pos, const
     hipMemcpyAsync(s->d_tri_nrm, tn.data(), tn.size() * sizeof(float4), hipMemcpyHostToDevice, st);
     if (hipMalloc(&s->d_mats, hm.size() * sizeof(float4)) != hipSuccess) return bail(RS_E_HIP, "hipMalloc(mats) failed");
     hipMemcpyAsync(s->d_mats, hm.data(), hm.size() * sizeof(float4), hipMemcpyHostToDevice, st);
+    if (s->n_emis) {
+        if (hipMalloc(&s->d_emis_tri, s->n_emis * sizeof(int)) != hipSuccess) return bail(RS_E_HIP, "hipMalloc(emis ids) failed");
+        hipMemcpyAsync(s->d_emis_tri, s->emis_tri.data(), s->n_emis * sizeof(int), hipMemcpyHostToDevice, st);
+    }
     if (build_geometry(c, s, pos, err) != 0) return bail(RS_E_HIP, err);
     *out = s;
     return RS_OK;
 }
 
-// Everything that depends on the vertex positions: the emissive-triangle table + CDF + guide table
-// (TriangleCDF ctor, pg/TriangleCDF.cpp:8-34, pg/TriangleCDF.h:25-31; Triangle::area,
-// pg/triangle.cpp:13-16) and the BVH.  Used at scene creation and by rs_scene_update_positions.
-static int build_geometry(rs_context* c, rs_scene* s, const std::vector<float>& pos, std::string& err) {
-    const uint32_t n = s->n_tris;
-    const std::vector<float>& nrm = s->h_nrm;
-    const std::vector<uint32_t>& tri_mat = s->h_tri_mat;
-    const rs_material_desc* mats = s->h_mats.data();
-    std::vector<uint32_t> emis_tri;
-    for (uint32_t t = 0; t < n; ++t) {
-        const rs_material_desc& d = mats[tri_mat[t]];
-        if (d.emission[0] + d.emission[1] + d.emission[2] > 0) emis_tri.push_back(t);   // same order as eid
-    }
+// Emitter buckets for the sorted initial pass (performance only: any bucketing gives the same frames): the emitters'
+// centroids in Morton order over their bounds, cut into 64 equal runs.  ebucket: one byte per emitter (one zero
+// without any); ecen: the centre of the centroids' bounds (left alone without emitters).
+static std::vector<uint8_t> emitter_buckets(const std::vector<float>& pos, const std::vector<uint32_t>& emis_tri, float ecen[3]) {
     const uint32_t ne = (uint32_t)emis_tri.size();
-    std::vector<float> area(ne), cdf(std::max(ne, 1u));
-    float total = 0.0f;
+    std::vector<uint8_t> ebucket(std::max(ne, 1u), 0);
+    if (!ne) return ebucket;
+    float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
+    std::vector<float> cen(3 * (size_t)ne);
     for (uint32_t e = 0; e < ne; ++e) {
         const float* p = &pos[9 * (size_t)emis_tri[e]];
-        hv3 a{p[0], p[1], p[2]}, b{p[3], p[4], p[5]}, cc{p[6], p[7], p[8]};
-        area[e] = 0.5f * hlen(hcross(hsub(b, a), hsub(cc, a)));
-        total += area[e];
-    }
-    for (uint32_t e = 0; e < ne; ++e) {
-        float na = area[e] / total;
-        float pred = e == 0 ? 0.0f : cdf[e - 1];
-        cdf[e] = pred + na;
-    }
-    std::vector<float4> em(8 * (size_t)std::max(ne, 1u));
-    for (uint32_t e = 0; e < ne; ++e) {
-        uint32_t t = emis_tri[e];
-        const float* p = &pos[9 * (size_t)t];
-        const float* q = &nrm[9 * (size_t)t];
-        const rs_material_desc& d = mats[tri_mat[t]];
-        float pick = e == 0 ? cdf[0] : cdf[e] - cdf[e - 1];
-        float inv_area = 1.0f / area[e];
-        float pdf_brdf = area[e] / total;
-        pdf_brdf *= 1.0f / area[e];
-        const bool flat = std::memcmp(q, q + 3, 3 * sizeof(float)) == 0 && std::memcmp(q, q + 6, 3 * sizeof(float)) == 0;
-        const float pdf_area = pick * inv_area;           // the product areaSampleLight forms (rs_passes.h EmisRec)
-        em[8 * e + 0] = make_float4(p[0], p[1], p[2], flat ? pdf_area : -pdf_area);
-        em[8 * e + 1] = make_float4(p[3], p[4], p[5], q[0]);
-        em[8 * e + 2] = make_float4(p[6], p[7], p[8], q[1]);
-        em[8 * e + 3] = make_float4(d.emission[0], d.emission[1], d.emission[2], q[2]);
-        em[8 * e + 4] = make_float4(q[3], q[4], q[5], pick);
-        em[8 * e + 5] = make_float4(q[6], q[7], q[8], pdf_brdf);
-        em[8 * e + 6] = make_float4(area[e], inv_area, 0.0f, 0.0f);
-        em[8 * e + 7] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    }
-    // emitter buckets for the sorted initial pass (performance only: any bucketing gives the same frames):
-    // the emitters' centroids in Morton order over their bounds, cut into 64 equal runs
-    std::vector<uint8_t> ebucket(std::max(ne, 1u), 0);
-    if (ne) {
-        float lo[3] = {3.0e38f, 3.0e38f, 3.0e38f}, hi[3] = {-3.0e38f, -3.0e38f, -3.0e38f};
-        std::vector<float> cen(3 * (size_t)ne);
-        for (uint32_t e = 0; e < ne; ++e) {
-            const float* p = &pos[9 * (size_t)emis_tri[e]];
-            for (int a = 0; a < 3; ++a) {
-                const float v = (p[a] + p[3 + a] + p[6 + a]) * (1.0f / 3.0f);
-                cen[3 * (size_t)e + a] = std::isfinite(v) ? v : 0.0f;
-                lo[a] = std::min(lo[a], cen[3 * (size_t)e + a]); hi[a] = std::max(hi[a], cen[3 * (size_t)e + a]);
-            }
+        for (int a = 0; a < 3; ++a) {
+            const float v = (p[a] + p[3 + a] + p[6 + a]) * (1.0f / 3.0f);
+            cen[3 * (size_t)e + a] = std::isfinite(v) ? v : 0.0f;
+            lo[a] = std::min(lo[a], cen[3 * (size_t)e + a]); hi[a] = std::max(hi[a], cen[3 * (size_t)e + a]);
         }
-        std::vector<std::pair<uint64_t, uint32_t>> ord(ne);
-        for (uint32_t e = 0; e < ne; ++e) {
-            uint64_t m = 0;
-            uint32_t q[3];
-            for (int a = 0; a < 3; ++a) {
-                const float ext = hi[a] - lo[a];
-                const float t = ext > 0.0f ? (cen[3 * (size_t)e + a] - lo[a]) / ext : 0.0f;
-                q[a] = (uint32_t)std::min(1023.0f, std::max(0.0f, t * 1024.0f));
-            }
-            for (int b = 0; b < 10; ++b)
-                for (int a = 0; a < 3; ++a) m |= (uint64_t)((q[a] >> b) & 1u) << (3 * b + a);
-            ord[e] = {m, e};
+    }
+    std::vector<std::pair<uint64_t, uint32_t>> ord(ne);
+    for (uint32_t e = 0; e < ne; ++e) {
+        uint64_t m = 0;
+        uint32_t q[3];
+        for (int a = 0; a < 3; ++a) {
+            const float ext = hi[a] - lo[a];
+            const float t = ext > 0.0f ? (cen[3 * (size_t)e + a] - lo[a]) / ext : 0.0f;
+            q[a] = (uint32_t)std::min(1023.0f, std::max(0.0f, t * 1024.0f));
         }
-        std::sort(ord.begin(), ord.end());
-        for (uint32_t i = 0; i < ne; ++i) ebucket[ord[i].second] = (uint8_t)(((uint64_t)i * 64u) / ne);
-        for (int a = 0; a < 3; ++a) s->ecen[a] = 0.5f * lo[a] + 0.5f * hi[a];
+        for (int b = 0; b < 10; ++b)
+            for (int a = 0; a < 3; ++a) m |= (uint64_t)((q[a] >> b) & 1u) << (3 * b + a);
+        ord[e] = {m, e};
     }
-    std::vector<int> guide(kCdfGuide + 1);     // guide[j] = lower_bound(cdf, j / kCdfGuide)
-    for (int j = 0; j <= kCdfGuide; ++j) {
-        float key = (float)j / (float)kCdfGuide;
-        guide[j] = (int)(std::lower_bound(cdf.begin(), cdf.begin() + ne, key) - cdf.begin());
-    }
-    hipStream_t st = c->stream;
-    c->join_next = true;
-    sync_all(c);                                // frames in flight, pipelined updates
-    if (hipStreamSynchronize(st) != hipSuccess) { err = "stream sync failed"; return -1; }
-    geo_free(s->alt);
-    if (s->a_tri_nrm) hipFree(s->a_tri_nrm);
-    s->a_tri_nrm = nullptr; s->a_geo = 0xffffffffu; s->a_nrm = false;
-    s->update_recorded = false;
-    geo_free(s->geo); s->wide_on = false;
-    void* old[] = {s->d_pos, s->d_emis_tri, s->d_refit_order, s->d_refit_lvl, s->d_ebucket};
-    for (void* p : old) if (p) hipFree(p);
-    s->d_pos = nullptr; s->d_ebucket = nullptr; s->d_emis_tri = nullptr; s->d_refit_order = nullptr; s->d_refit_lvl = nullptr;
-    s->n_nodes = 0; s->refit_lvl.clear();
-    s->n_emis = ne;
-    auto upload = [&](auto** d, const void* h, size_t bytes, const char* what) {
-        if (hipMalloc(d, bytes) != hipSuccess) { err = std::string("hipMalloc(") + what + ") failed"; return false; }
-        hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, st);
-        return true;
-    };
-    if ((n && !upload(&s->d_pos, pos.data(), pos.size() * sizeof(float), "pos")) ||
-        !upload(&s->geo.emis, em.data(), em.size() * sizeof(float4), "emis") || !upload(&s->geo.cdf, cdf.data(), cdf.size() * sizeof(float), "cdf") ||
-        !upload(&s->geo.cdf_guide, guide.data(), guide.size() * sizeof(int), "guide") ||
-        !upload(&s->d_ebucket, ebucket.data(), ebucket.size(), "emitter buckets") ||
-        (ne && !upload(&s->d_emis_tri, emis_tri.data(), ne * sizeof(int), "emis ids"))) return -1;
-    if (hipStreamSynchronize(st) != hipSuccess) { err = "geometry upload failed"; return -1; }   // host vectors die
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0); hipEventCreate(&e1);
-    hipEventRecord(e0, st);
-    std::string berr;
-    s->box_eps = box_epsilon(pos.data(), pos.size());
-    int rc = build_bvh(s->d_pos, n, st, &s->geo.nodes, &s->n_nodes, &s->geo.tris, &s->geo.wide, berr);
-    s->wide_on = rc == 0 && s->geo.wide.n_nodes > 0 && s->geo.wide.depth <= kWideStack;   // deeper: the skip pointers
-    hipEventRecord(e1, st);
-    if (rc == 0 && hipStreamSynchronize(st) == hipSuccess) hipEventElapsedTime(&s->build_ms, e0, e1);
-    else { err = "BVH build failed: " + berr; rc = -1; (void)hipStreamSynchronize(st); }
-    builder_pool_trim();                          // the build's scratch back to the driver (stream drained above)
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    if (rc == 0 && bvh_refit_plan(s->geo.nodes, s->n_nodes, st, &s->d_refit_order, &s->d_refit_lvl, s->refit_lvl, berr) != 0) {
-        err = berr; rc = -1;
-    }
-    return rc;
+    std::sort(ord.begin(), ord.end());
+    for (uint32_t i = 0; i < ne; ++i) ebucket[ord[i].second] = (uint8_t)(((uint64_t)i * 64u) / ne);
+    for (int a = 0; a < 3; ++a) ecen[a] = 0.5f * lo[a] + 0.5f * hi[a];
+    return ebucket;
 }
 
-// TriangleCDF tables from the positions on the device (rs_scene_update_positions): the same float
-// operations in the same order as build_geometry's host loop -- sequential total and prefix sum in
-// one lane, everything else data-parallel -- so the tables are bit-identical to a fresh scene's.
+// The emissive-triangle table + CDF + guide table from the positions, on the device: the one builder, for scene
+// creation, rs_scene_rebuild and rs_scene_update_positions.  The float operations and their order are the
+// reference's (TriangleCDF ctor, pg/TriangleCDF.cpp:8-34, pg/TriangleCDF.h:25-31; Triangle::area,
+// pg/triangle.cpp:13-16) as the oracle restates them (or_scene_cdf) -- sequential total and prefix sum in one lane,
+// everything else data-parallel -- and tests/test_gpu_light_tables.py holds the tables to the oracle's bit for bit.
 constexpr int kLightBlock = kRefitBlock, kLightChunk = 8192;
 __device__ __forceinline__ void light_table(const float* __restrict__ pos, const float4* __restrict__ tri_nrm,
                                             const float4* __restrict__ mats, const int* __restrict__ emis_tri,
@@ -983,14 +895,18 @@ static int wide_copy(rs_context* c, const WideBvh& from, WideBvh& to, hipStream_
     return RS_OK;
 }
 
-// a GeoCopy's buffers from sizes (its 8-wide tree comes with the first geo_copy: wide_copy)
-static int geo_alloc(rs_context* c, GeoCopy& g, const GeoBytes& b) {
-    HIPCHK(c, hipMalloc(&g.nodes, b.nodes));
-    HIPCHK(c, hipMalloc(&g.tris, b.tris));
+// a GeoCopy's light tables from sizes (a scene without emitters keeps one float4 of records and one CDF entry)
+static int tables_alloc(rs_context* c, GeoCopy& g, const GeoBytes& b) {
     HIPCHK(c, hipMalloc(&g.emis, std::max<size_t>(b.emis, sizeof(float4))));
     HIPCHK(c, hipMalloc(&g.cdf, b.cdf));
     HIPCHK(c, hipMalloc(&g.cdf_guide, b.guide));
     return RS_OK;
+}
+// a GeoCopy's buffers from sizes (its 8-wide tree comes with the first geo_copy: wide_copy)
+static int geo_alloc(rs_context* c, GeoCopy& g, const GeoBytes& b) {
+    HIPCHK(c, hipMalloc(&g.nodes, b.nodes));
+    HIPCHK(c, hipMalloc(&g.tris, b.tris));
+    return tables_alloc(c, g, b);
 }
 // device-to-device on `st`: the trees (the 8-wide one when live), and with `tables` the light tables
 static int geo_copy(rs_context* c, const GeoCopy& from, GeoCopy& to, const GeoBytes& b, bool wide, bool tables, hipStream_t st) {
@@ -1008,6 +924,67 @@ static void geo_free(GeoCopy& g) {
     for (void* p : own) if (p) hipFree(p);
     wide_free(g.wide);
     g.nodes = g.tris = g.emis = nullptr; g.cdf = nullptr; g.cdf_guide = nullptr;
+}
+
+// Everything that depends on the vertex positions, for scene creation and rs_scene_rebuild: the positions' device
+// copy, the light tables (light_table, the builder rs_scene_update_positions runs too), the emitter buckets, the
+// closest-hit box margin, the trees and the refit plan.  build_ms times build_bvh alone.
+static int build_geometry(rs_context* c, rs_scene* s, const std::vector<float>& pos, std::string& err) {
+    const uint32_t n = s->n_tris, ne = s->n_emis;
+    hipStream_t st = c->stream;
+    // 1. drain: frames in flight, pipelined updates
+    c->join_next = true;
+    sync_all(c);
+    if (hipStreamSynchronize(st) != hipSuccess) { err = "stream sync failed"; return -1; }
+    // 2. the old copies go
+    geo_free(s->alt);
+    if (s->a_tri_nrm) hipFree(s->a_tri_nrm);
+    s->a_tri_nrm = nullptr; s->a_geo = 0xffffffffu; s->a_nrm = false;
+    s->update_recorded = false;
+    geo_free(s->geo); s->wide_on = false;
+    void* old[] = {s->d_pos, s->d_refit_order, s->d_refit_lvl, s->d_ebucket};
+    for (void* p : old) if (p) hipFree(p);
+    s->d_pos = nullptr; s->d_ebucket = nullptr; s->d_refit_order = nullptr; s->d_refit_lvl = nullptr;
+    s->n_nodes = 0; s->refit_lvl.clear();
+    auto upload = [&](auto** d, const void* h, size_t bytes, const char* what) {
+        if (hipMalloc(d, bytes) != hipSuccess) { err = std::string("hipMalloc(") + what + ") failed"; return false; }
+        hipMemcpyAsync(*d, h, bytes, hipMemcpyHostToDevice, st);
+        return true;
+    };
+    // 3. positions
+    if (n && !upload(&s->d_pos, pos.data(), pos.size() * sizeof(float), "pos")) return -1;
+    // 4. light tables: workgroup 0's job of the update kernel alone (no refit batches), or the zero placeholders
+    const GeoBytes gb = s->geo_bytes();
+    if (tables_alloc(c, s->geo, gb) != RS_OK) { err = c->err; return -1; }
+    if (ne) {
+        k_scene_update<<<1, kLightBlock, 0, st>>>(s->d_pos, s->d_tri_nrm, s->d_mats, s->d_emis_tri, ne, s->geo.emis, s->geo.cdf,
+                                                  s->geo.cdf_guide, RefitArgs{}, WideRefitArgs{});
+    } else {
+        hipMemsetAsync(s->geo.emis, 0, sizeof(float4), st);
+        hipMemsetAsync(s->geo.cdf, 0, gb.cdf, st);
+        hipMemsetAsync(s->geo.cdf_guide, 0, gb.guide, st);
+    }
+    // 5. emitter buckets
+    const std::vector<uint8_t> ebucket = emitter_buckets(pos, s->emis_tri, s->ecen);
+    if (!upload(&s->d_ebucket, ebucket.data(), ebucket.size(), "emitter buckets")) return -1;
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { err = "geometry upload failed"; return -1; }
+    // 6. box margin, 7. trees (timed), 8. refit plan
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    hipEventRecord(e0, st);
+    std::string berr;
+    s->box_eps = box_epsilon(pos.data(), pos.size());
+    int rc = build_bvh(s->d_pos, n, st, &s->geo.nodes, &s->n_nodes, &s->geo.tris, &s->geo.wide, berr);
+    s->wide_on = rc == 0 && s->geo.wide.n_nodes > 0 && s->geo.wide.depth <= kWideStack;   // deeper: the skip pointers
+    hipEventRecord(e1, st);
+    if (rc == 0 && hipStreamSynchronize(st) == hipSuccess) hipEventElapsedTime(&s->build_ms, e0, e1);
+    else { err = "BVH build failed: " + berr; rc = -1; (void)hipStreamSynchronize(st); }
+    builder_pool_trim();                          // the build's scratch back to the driver (stream drained above)
+    hipEventDestroy(e0); hipEventDestroy(e1);
+    if (rc == 0 && bvh_refit_plan(s->geo.nodes, s->n_nodes, st, &s->d_refit_order, &s->d_refit_lvl, s->refit_lvl, berr) != 0) {
+        err = berr; rc = -1;
+    }
+    return rc;
 }
 
 __global__ void k_set_normals(const float* __restrict__ nrm, uint32_t n, float4* tri_nrm) {
@@ -1080,7 +1057,6 @@ extern "C" int rs_scene_update_positions(rs_scene* s, const float* positions, co
     s->geo_gen++;
     HIPCHK(c, hipMemcpyAsync(s->d_pos, s->h_stage[k], nf * sizeof(float), hipMemcpyHostToDevice, st));
     if (normals) {
-        s->h_nrm.assign(normals, normals + nf);
         if (!s->d_nrm_stage) HIPCHK(c, hipMalloc(&s->d_nrm_stage, nf * sizeof(float)));
         std::memcpy(s->h_stage[k] + nf, normals, nf * sizeof(float));
         HIPCHK(c, hipMemcpyAsync(s->d_nrm_stage, s->h_stage[k] + nf, nf * sizeof(float), hipMemcpyHostToDevice, st));
@@ -1118,8 +1094,8 @@ extern "C" int rs_scene_update_positions(rs_scene* s, const float* positions, co
     return RS_OK;
 }
 
-// Full rebuild (light tables on the host + a new PLOC tree) from the scene's current device positions:
-// restores tree quality after large motions.  Synchronous.
+// Full rebuild (light tables + a new PLOC tree) from the scene's current device positions, read back for the box
+// margin and the emitter buckets: restores tree quality after large motions.  Synchronous.
 extern "C" int rs_scene_rebuild(rs_scene* s) {
     if (!s) return fail(nullptr, RS_E_INVALID, "rs_scene_rebuild: null scene");
     rs_context* c = s->ctx;
@@ -1296,6 +1272,21 @@ extern "C" int rs_debug_bvh_tree(const rs_scene* s, uint32_t* n_nodes, uint32_t*
     if (s->update_recorded) HIPCHK(c, hipStreamWaitEvent(c->stream, s->update_ev, 0));   // a pipelined update
     if (nodes) HIPCHK(c, hipMemcpyAsync(nodes, s->geo.nodes, (size_t)s->n_nodes * 2 * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     return read_prims(c, s->geo.tris, s->n_tris, prims);
+}
+
+extern "C" int rs_debug_light_tables(const rs_scene* s, uint32_t* n_emis, float* em, float* cdf, int32_t* guide) {
+    if (!s || !n_emis) return fail(s ? s->ctx : nullptr, RS_E_INVALID, "rs_debug_light_tables: null argument");
+    rs_context* c = s->ctx;
+    HIPCHK(c, enter(c));
+    *n_emis = s->n_emis;
+    if (!em && !cdf && !guide) return RS_OK;
+    if (s->update_recorded) HIPCHK(c, hipStreamWaitEvent(c->stream, s->update_ev, 0));   // a pipelined update
+    const GeoBytes gb = s->geo_bytes();
+    if (em && gb.emis) HIPCHK(c, hipMemcpyAsync(em, s->geo.emis, gb.emis, hipMemcpyDeviceToHost, c->stream));
+    if (cdf && s->n_emis) HIPCHK(c, hipMemcpyAsync(cdf, s->geo.cdf, (size_t)s->n_emis * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (guide) HIPCHK(c, hipMemcpyAsync(guide, s->geo.cdf_guide, gb.guide, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RS_OK;
 }
 
 extern "C" int rs_scene_walk_info(const rs_scene* s, uint32_t* wide_nodes, int32_t* wide_depth, int32_t* status) {

@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = [
     "rs_denoiser_check_weights", "rs_denoiser_create", "rs_denoiser_create_from_file", "rs_denoiser_info_get",
     "rs_denoiser_execute", "rs_denoise_frame", "rs_context_set_denoiser", "rs_denoiser_set_timing",
     "rs_denoiser_last_ms", "rs_denoiser_layer_ms", "rs_denoiser_get_scale", "rs_denoiser_dump", "rs_denoiser_destroy",
-    "rs_render_path", "rs_debug_bvh_tree",
+    "rs_render_path", "rs_debug_bvh_tree", "rs_debug_light_tables",
 ]
 
 # BVH traversal kinds (include/restir_c.h RS_TRAVERSAL_*)
@@ -176,6 +176,8 @@ def load_library(path: str = LIB_PATH):
     L.rs_debug_wide_tree.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_int32), vp, vp]
     if hasattr(L, "rs_debug_bvh_tree"):          # (absent from earlier builds, which A/Bs load)
         L.rs_debug_bvh_tree.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), vp, vp]
+    if hasattr(L, "rs_debug_light_tables"):
+        L.rs_debug_light_tables.argtypes = [vp, ctypes.POINTER(u32), vp, vp, vp]
     L.rs_scene_walk_info.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]
     L.rs_context_set_traversal.argtypes = [vp, i32]
     ip = ctypes.POINTER(ctypes.c_int32)
@@ -379,6 +381,19 @@ class Scene:
             r._check(r.lib.rs_debug_bvh_tree(self.h, ctypes.byref(nn), ctypes.byref(nt),
                                              nodes.ctypes.data_as(ctypes.c_void_p), prims.ctypes.data_as(ctypes.c_void_p)))
         return nodes, prims
+
+    def debug_light_tables(self):
+        """Test hook (rs_debug_light_tables): the scene's current light tables as (records (n_emis, 8, 4) float32 --
+        include/restir_c.h has the layout --, cdf (n_emis,) float32, guide (1025,) int32)."""
+        r = self.renderer
+        ne = ctypes.c_uint32()
+        r._check(r.lib.rs_debug_light_tables(self.h, ctypes.byref(ne), None, None, None))
+        em = np.zeros((ne.value, 8, 4), np.float32)
+        cdf = np.zeros(ne.value, np.float32)
+        guide = np.zeros(1025, np.int32)
+        r._check(r.lib.rs_debug_light_tables(self.h, ctypes.byref(ne), em.ctypes.data_as(ctypes.c_void_p),
+                                             cdf.ctypes.data_as(ctypes.c_void_p), guide.ctypes.data_as(ctypes.c_void_p)))
+        return em, cdf, guide
 
     def close(self):
         if self.h:
