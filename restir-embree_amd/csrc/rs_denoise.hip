@@ -14,13 +14,15 @@
 // the one GEMM-shaped workload of the renderer, so it runs on MFMA:
 //   * activations: NHWC float16, channels padded to a multiple of 16, every level's tensor stored with a
 //     one-pixel zero border (the convolutions' zero padding; the border is never written);
-//   * one kernel per convolution, an implicit GEMM: a workgroup (4 waves) computes a 16x16-pixel output
-//     tile for all output channels; the input halo (18x18 pixels x 32 channels) is staged in LDS (two
-//     buffers: the next channel chunk's global loads are in flight while the MFMAs run on this one;
-//     XOR-swizzled 16-B slots so a wave's fragment reads are bank-conflict free); each wave owns 8x8
-//     pixels = 4 groups of 16 (2x2 quads side by side), A fragments (16 pixels x 32 k) come from LDS, B
-//     fragments (32 k x 16 output channels) are pre-packed per lane on the host so each is one coalesced
-//     1-KB load; v_mfma_f32_16x16x32_f16, float32 accumulation;
+//   * one kernel per convolution, an implicit GEMM (k_conv3): a workgroup (4 waves) computes a 16x16-pixel
+//     output tile for NT x 16 output channels; the input halo (18x18 pixels x 32 channels) is staged in one
+//     LDS buffer, linear: 64-B pixels at a 1312-B row pitch, at which every fragment read is bank-conflict
+//     free; each wave owns 8x8 pixels = 4 groups of 16 (2x2 quads side by side), A fragments (16 pixels x
+//     32 k) come from LDS; B fragments (32 k x 16 output channels) are pre-packed per lane on the host (one
+//     fragment = 1 KB contiguous) and staged once per workgroup through LDS next to the halo, in stages of
+//     5 or 9 k-steps (BStage); the next stage's global loads (halo and B) are in registers while the MFMAs
+//     run on this one, then two barriers around the LDS writes; v_mfma_f32_16x16x32_f16, float32
+//     accumulation;
 //   * a k-step is one tap x 32 channels, or -- for 16-channel chunks (the 9-channel input, the odd half of
 //     48 / 80 / 112-channel tensors) -- two taps x 16 channels;
 //   * fused: bias + ReLU; 2x2 max pooling (a lane's 4 accumulator registers ARE a 2x2 quad); the
@@ -38,6 +40,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/restir_c.h"
@@ -80,7 +83,8 @@ constexpr int kRowBytes = kHalo * 64 + 160;    // 1312
 constexpr int kChunkBytes = kHalo * kRowBytes; // 23616 B
 constexpr int kMaxChunks = 12;
 constexpr int kStageRegs = (kHaloPx * 4 + 255) / 256;   // 16-B staging slots per thread (6)
-constexpr size_t kFillWorkgroups = 256;                   // one workgroup per CU before splitting channels
+constexpr size_t kFillWorkgroups = 256;                   // one workgroup per CU before splitting channels: the
+                                                          // default of RESTIR_DN_FILL
                                                           // (splitting re-stages the halo: measured slower
                                                           // at 1/4 resolution, faster only at 1/16)
 constexpr int kMaxNtw = 4;                                // n-tiles per workgroup: 16 x 4 accumulators per lane
@@ -106,71 +110,68 @@ struct ConvArgs {
     float inv_norm;            // 1 / NORM_SCALE = pu_forward(65504)
 };
 
+// 16-B slot q of a chunk's halo image (spp slots per pixel): halo pixel (hr, hc), 8-channel part sl
+struct HaloSlot { int hr, hc, sl; };
+__device__ __forceinline__ HaloSlot halo_slot(int q, int spp) {
+    const int px = spp == 4 ? (q >> 2) : (q >> 1), hr = px / kHalo;
+    return HaloSlot{hr, px - hr * kHalo, q & (spp - 1)};
+}
 __device__ __forceinline__ void stage_load(const ConvArgs& a, int c, int tx0, int ty0, uint4 (&r)[kStageRegs]) {
     const int s = a.ch_src[c];
     const int spp = a.ch_w[c] >> 3;            // 16-B slots per pixel: 4 (32 ch) or 2 (16 ch)
     const _Float16* src = a.src[s];
     const int cs = a.cs[s], sh = a.sh[s], sw = a.sw[s], up = a.up[s], base = a.ch_base[c];
-    const int nslots = kHaloPx * spp;
 #pragma unroll
     for (int k = 0; k < kStageRegs; ++k) {
         const int q = (int)threadIdx.x + k * 256;
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (q < nslots) {
-            const int px = spp == 4 ? (q >> 2) : (q >> 1), sl = q & (spp - 1);
-            const int hr = px / kHalo, hc = px - hr * kHalo;
-            int y = ty0 - 1 + hr, x = tx0 - 1 + hc;
+        if (q < kHaloPx * spp) {
+            const HaloSlot p = halo_slot(q, spp);
+            int y = ty0 - 1 + p.hr, x = tx0 - 1 + p.hc;
             if (up) { y >>= 1; x >>= 1; }      // arithmetic: -1 stays -1 (the border)
             if (y >= -1 && y <= sh && x >= -1 && x <= sw)
-                v = *(const uint4*)(src + ((size_t)(y + 1) * (size_t)(sw + 2) + (size_t)(x + 1)) * cs + base + 8 * sl);
+                v = *(const uint4*)(src + ((size_t)(y + 1) * (size_t)(sw + 2) + (size_t)(x + 1)) * cs + base + 8 * p.sl);
         }
         r[k] = v;
     }
 }
 __device__ __forceinline__ void stage_store(uint8_t* buf, int spp, const uint4 (&r)[kStageRegs]) {
-    const int nslots = kHaloPx * spp;
 #pragma unroll
     for (int k = 0; k < kStageRegs; ++k) {
         const int q = (int)threadIdx.x + k * 256;
-        if (q < nslots) {
-            const int px = spp == 4 ? (q >> 2) : (q >> 1), sl = q & (spp - 1);
-            const int hr = px / kHalo, hc = px - hr * kHalo;
-            *(uint4*)(buf + hr * kRowBytes + hc * 64 + (sl << 4)) = r[k];
+        if (q < kHaloPx * spp) {
+            const HaloSlot p = halo_slot(q, spp);
+            *(uint4*)(buf + p.hr * kRowBytes + p.hc * 64 + (p.sl << 4)) = r[k];
         }
     }
 }
 
-// B fragments: all four waves of a workgroup multiply the same weights, so a chunk's B fragments are
-// staged once per workgroup into LDS ([step][n-tile][64 lanes] x 16 B, a wave's fragment read = 1 KB
-// contiguous: conflict-free) instead of each wave loading them from L2 -- the per-wave loads were 6x the
-// halo staging's vector-memory instructions and kept the texture data path 82 % busy (r03_pmc_denoise).
-// Halo and B buffers are single: loads of chunk c + 1 into registers overlap chunk c's MFMAs, then two
-// barriers around the LDS writes.
-// Only for NT <= 3: a 4-n-tile chunk's 36 KB of B would leave 2 workgroups per CU (measured slower on
-// dec_conv1a: 247 vs 219 us); those keep per-wave global B loads (next step's prefetched) and a
-// double-buffered halo.
-#ifndef RS_DN_HALFB
-#define RS_DN_HALFB 1
-#endif
-template <int NT> struct BStage { static constexpr bool lds = NT <= 3 && !(RS_DN_HALFB && NT == 2); static constexpr int kRegs = lds ? (9 * NT * 64 + 255) / 256 : 1; };
-// NT = 4 and 2: B staged through LDS in two stages per 32-channel chunk (steps 0-4, then 5-8: 5 NT KB at a
-// time): NT = 4 keeps the LDS budget of the per-wave-B form (3 workgroups per CU) without its per-wave B
-// loads, NT = 2 fits 4 workgroups per CU instead of 3 (whole-chunk staging).  NT = 1 and 3 gain nothing
-// from it (measured: equal; NT = 3 is register-bound at 3 waves)
-#ifndef RS_DN_B4_STEPS
-#define RS_DN_B4_STEPS 5
-#endif
-template <int NT> struct BHalf { static constexpr bool on = RS_DN_HALFB && (NT == 4 || NT == 2);
-                                 static constexpr int steps = NT == 4 ? RS_DN_B4_STEPS : 5;   // k-steps per LDS stage
-                                 static constexpr int waves = NT == 4 && steps > 3 ? 3 : 4;   // per SIMD (= workgroups per CU by LDS)
-                                 static constexpr int kRegs = (steps * NT * 64 + 255) / 256; };
+// B fragments: all four waves of a workgroup multiply the same weights, so they are staged once per
+// workgroup into LDS ([step][n-tile][64 lanes] x 16 B, a wave's fragment read = 1 KB contiguous:
+// conflict-free) instead of each wave loading them from L2 -- the per-wave loads were 6x the halo staging's
+// vector-memory instructions and kept the texture data path 82 % busy (r03_pmc_denoise).  Halo and B
+// buffers are single: the next stage's loads into registers overlap this stage's MFMAs, then two barriers
+// around the LDS writes.
+// A stage is `steps` k-steps of a chunk.  NT = 4 and 2: two stages per 32-channel chunk (steps 0-4, then
+// 5-8: 5 NT KB at a time) -- at NT = 4 a whole chunk's 36 KB of B would leave 2 workgroups per CU (measured
+// slower on dec_conv1a: 247 vs 219 us) where 20 KB keeps 3, and NT = 2 fits 4 workgroups per CU instead
+// of 3.  NT = 1 and 3: the whole chunk in one stage (two stages measured equal; NT = 3 is register-bound
+// at 3 waves).  `waves` is the launch bound per SIMD (= workgroups per CU by LDS).  The arms measured
+// slower (each wave loading its B from global with a double-buffered halo, and three stages
+// of 3 k-steps at NT = 4) were two build switches until round 18; they can be rebuilt from
+// commit 34e104b.
+template <int NT> struct BStage {
+    static constexpr int steps = NT == 4 || NT == 2 ? 5 : 9;
+    static constexpr int waves = NT == 4 ? 3 : NT == 2 ? 4 : 1;
+    static constexpr int kRegs = (steps * NT * 64 + 255) / 256;
+};
 // B fragments of steps [s0, s0 + ns) of chunk c into registers / from registers into bbuf (step s0 first)
 template <int NT>
-__device__ __forceinline__ void bhalf_load(const ConvArgs& a, int c, int n0, int s0, int ns, uint4 (&r)[BHalf<NT>::kRegs]) {
-    const int n = ns * NT * 64;
+__device__ __forceinline__ void bstage_load(const ConvArgs& a, int c, int n0, int s0, int ns, uint4 (&r)[BStage<NT>::kRegs]) {
+    const int n = ns * NT * 64;                // 16-B pieces: (step, n-tile, lane)
     const uint4* w = (const uint4*)a.w;
 #pragma unroll
-    for (int k = 0; k < BHalf<NT>::kRegs; ++k) {
+    for (int k = 0; k < BStage<NT>::kRegs; ++k) {
         const int q = (int)threadIdx.x + k * 256;
         uint4 v = make_uint4(0u, 0u, 0u, 0u);
         if (q < n) {
@@ -181,96 +182,87 @@ __device__ __forceinline__ void bhalf_load(const ConvArgs& a, int c, int n0, int
     }
 }
 template <int NT>
-__device__ __forceinline__ void bhalf_store(uint8_t* bbuf, int ns, const uint4 (&r)[BHalf<NT>::kRegs]) {
+__device__ __forceinline__ void bstage_store(uint8_t* bbuf, int ns, const uint4 (&r)[BStage<NT>::kRegs]) {
     const int n = ns * NT * 64;
 #pragma unroll
-    for (int k = 0; k < BHalf<NT>::kRegs; ++k) {
-        const int q = (int)threadIdx.x + k * 256;
-        if (q < n) *(uint4*)(bbuf + q * 16) = r[k];
-    }
-}
-
-template <int NT>
-__device__ __forceinline__ void bstage_load(const ConvArgs& a, int c, int n0, uint4 (&r)[BStage<NT>::kRegs]) {
-    const int nst = a.ch_w[c] == 32 ? 9 : 5;
-    const int n = nst * NT * 64;               // 16-B pieces: (step, n-tile, lane)
-    const uint4* w = (const uint4*)a.w;
-#pragma unroll
-    for (int k = 0; k < BStage<NT>::kRegs; ++k) {
-        const int q = (int)threadIdx.x + k * 256;
-        uint4 v = make_uint4(0u, 0u, 0u, 0u);
-        if (q < n) {
-            const int st = q / (NT * 64), rem = q - st * (NT * 64);
-            v = w[((size_t)(a.ch_step[c] + st) * a.nt_total + n0) * 64 + rem];
-        }
-        r[k] = v;
-    }
-}
-template <int NT>
-__device__ __forceinline__ void bstage_store(uint8_t* bbuf, int nst, const uint4 (&r)[BStage<NT>::kRegs]) {
-    const int n = nst * NT * 64;
-#pragma unroll
     for (int k = 0; k < BStage<NT>::kRegs; ++k) {
         const int q = (int)threadIdx.x + k * 256;
         if (q < n) *(uint4*)(bbuf + q * 16) = r[k];
     }
 }
 
-// steps [s0, s1) of chunk c (s1 < 0: all); BL: B fragments from bbuf (step s0 first), else per wave from global
-template <int NT, bool BL = BStage<NT>::lds || BHalf<NT>::on>
+// one k-step of a wave: its NT B fragments from bp (n-tile n at + 64 n), then for each of its 4 pixel groups
+// the A fragment (group g at a0 + 2 g halo rows of `pitch` bytes) times every B fragment
+template <int NT>
+__device__ __forceinline__ void kstep(f32x4 (&acc)[4][NT], const uint8_t* a0, int pitch, const half8* bp) {
+    half8 b[NT];
+#pragma unroll
+    for (int n = 0; n < NT; ++n) b[n] = bp[n * 64];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const half8 av = *(const half8*)(a0 + 2 * g * pitch);
+#pragma unroll
+        for (int n = 0; n < NT; ++n) acc[g][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, b[n], acc[g][n], 0, 0, 0);
+    }
+}
+
+// steps [s0, s1) of chunk c on the halo image in buf and the B fragments in bbuf (step s0 first)
+template <int NT>
 __device__ __forceinline__ void compute_chunk(const ConvArgs& a, int c, const uint8_t* buf, const uint8_t* bbuf,
-                                              f32x4 (&acc)[4][NT], int lane, int X, int Yb, int n0, int s0 = 0,
-                                              int s1 = -1) {
+                                              f32x4 (&acc)[4][NT], int lane, int X, int Yb, int s0, int s1) {
     const int h = lane >> 4;
     const bool w32 = a.ch_w[c] == 32;
-    const int nst = s1 >= 0 ? s1 : (w32 ? 9 : 5);
-    const half8* bp = (const half8*)bbuf + lane - s0 * NT * 64;                       // BL
-    const half8* wp = a.w + ((size_t)a.ch_step[c] * a.nt_total + n0) * 64 + lane;     // otherwise
-    half8 bg[NT];
-    if constexpr (!BL)
-#pragma unroll
-        for (int n = 0; n < NT; ++n) bg[n] = wp[n * 64];
-    for (int st = s0; st < nst; ++st) {
+    const half8* bp = (const half8*)bbuf + lane - s0 * NT * 64;
+    for (int st = s0; st < s1; ++st) {
         int tap, sl;
         if (w32) { tap = st; sl = h; }
         else { tap = 2 * st + (h >> 1); tap = tap > 8 ? 8 : tap; sl = h & 1; }   // tap 9: zero weights
         const int ky = tap / 3, kx = tap - 3 * ky;
-        half8 b[NT], bn[NT];
-        if constexpr (BL) {
+        kstep<NT>(acc, buf + (Yb + ky) * kRowBytes + (X + kx) * 64 + (sl << 4), kRowBytes, bp + st * NT * 64);
+    }
+}
+
+// the epilogue's LDS image of a tile: bias + ReLU (POST_POOL: of the lane's 2x2 maximum) as float16, pixel
+// (x, y) of an OW-wide tile at (y * OW + x) * (NT * 16 + 8) halves.  C/D: lane holds column co = 16 n + i
+// and rows 4 h + r (r = register): pixel (2 h + (r & 1), r >> 1) of the group's 8x2 block -- one 2x2 quad
+// per lane.  The pixel pitch is 16 B more than the channels, so the 4 quads of a wave-instruction's
+// scattered 2-B writes fall on different banks.
+template <int NT, int POST, int OW>
+__device__ __forceinline__ void tile_image(_Float16* o, const f32x4 (&acc)[4][NT], const float (&bv)[NT], int wy,
+                                           int wx, int h, int i) {
+    constexpr int CP = NT * 16 + 8;
 #pragma unroll
-            for (int n = 0; n < NT; ++n) b[n] = bp[(st * NT + n) * 64];
-        } else {
-#pragma unroll
-            for (int n = 0; n < NT; ++n) b[n] = bg[n];
-            if (st + 1 < nst)
-#pragma unroll
-                for (int n = 0; n < NT; ++n) bn[n] = wp[((st + 1) * a.nt_total + n) * 64];
-        }
+    for (int n = 0; n < NT; ++n)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const int hr = Yb + 2 * g + ky, hc = X + kx;
-            const half8 av = *(const half8*)(buf + hr * kRowBytes + hc * 64 + (sl << 4));
+            if constexpr (POST == POST_POOL) {
+                const f32x4 v4 = acc[g][n];
+                float m = fmaxf(fmaxf(v4[0], v4[1]), fmaxf(v4[2], v4[3])) + bv[n];
+                m = m > 0.0f ? m : 0.0f;
+                o[((4 * wy + g) * OW + 4 * wx + h) * CP + 16 * n + i] = (_Float16)m;
+            } else {
 #pragma unroll
-            for (int n = 0; n < NT; ++n) acc[g][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, b[n], acc[g][n], 0, 0, 0);
+                for (int r = 0; r < 4; ++r) {
+                    float v = acc[g][n][r] + bv[n];
+                    v = v > 0.0f ? v : 0.0f;
+                    o[((8 * wy + 2 * g + (r >> 1)) * OW + 8 * wx + 2 * h + (r & 1)) * CP + 16 * n + i] = (_Float16)v;
+                }
+            }
         }
-        if constexpr (!BL)
-#pragma unroll
-            for (int n = 0; n < NT; ++n) bg[n] = bn[n];
-    }
 }
 
 template <int NT, int POST>
 struct ConvLds {
-    static constexpr int kB = 9 * NT * 1024;   // one chunk's B fragments
-    static constexpr int kIn = BStage<NT>::lds ? kChunkBytes + kB
-                             : BHalf<NT>::on ? kChunkBytes + BHalf<NT>::steps * NT * 1024 : 2 * kChunkBytes;
+    static constexpr int kIn = kChunkBytes + BStage<NT>::steps * NT * 1024;   // the halo image + one stage's B fragments
     static constexpr int kOut = POST == POST_STORE ? 256 * (NT * 16 + 8) * 2 : POST == POST_POOL ? 64 * (NT * 16 + 8) * 2
                                                                                      : 256 * 17 * 4;
     static constexpr int kBytes = kIn > kOut ? kIn : kOut;
 };
 
-template <int NT, int POST, bool RELU>
-__global__ void __launch_bounds__(256, BHalf<NT>::on ? BHalf<NT>::waves : 1) k_conv3(ConvArgs a) {
+// POST_STORE / POST_POOL: bias + ReLU (+ 2x2 max pooling) into the output tensor; POST_FINAL: dec_conv0,
+// linear, + the output transform
+template <int NT, int POST>
+__global__ void __launch_bounds__(256, BStage<NT>::waves) k_conv3(ConvArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t lds[ConvLds<NT, POST>::kBytes];
     uint8_t* const bbuf = lds + kChunkBytes;
     const int tx0 = blockIdx.x * kTile, ty0 = blockIdx.y * kTile;
@@ -288,134 +280,67 @@ __global__ void __launch_bounds__(256, BHalf<NT>::on ? BHalf<NT>::waves : 1) k_c
 #pragma unroll
         for (int n = 0; n < NT; ++n) acc[g][n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 
-    uint4 st[kStageRegs];
-    if constexpr (BStage<NT>::lds) {           // single halo + B buffers, two barriers per chunk
-        uint4 bs[BStage<NT>::kRegs];
-        stage_load(a, 0, tx0, ty0, st);
-        bstage_load<NT>(a, 0, n0, bs);
-        stage_store(lds, a.ch_w[0] >> 3, st);
-        bstage_store<NT>(bbuf, a.ch_w[0] == 32 ? 9 : 5, bs);
-        __syncthreads();
-        for (int c = 0; c < a.nchunk; ++c) {
-            const bool more = c + 1 < a.nchunk;
-            if (more) {                        // in flight during the MFMAs
-                stage_load(a, c + 1, tx0, ty0, st);
-                bstage_load<NT>(a, c + 1, n0, bs);
-            }
-            compute_chunk<NT>(a, c, lds, bbuf, acc, lane, X, Yb, n0);
-            __syncthreads();
-            if (more) {
-                stage_store(lds, a.ch_w[c + 1] >> 3, st);
-                bstage_store<NT>(bbuf, a.ch_w[c + 1] == 32 ? 9 : 5, bs);
-                __syncthreads();
-            }
-        }
-    } else if constexpr (BHalf<NT>::on) {      // single halo buffer, B in LDS stages of S k-steps
-        constexpr int S = BHalf<NT>::steps;
-        uint4 bs[BHalf<NT>::kRegs];
-        auto nsteps = [&](int c) { return a.ch_w[c] == 32 ? 9 : 5; };
-        stage_load(a, 0, tx0, ty0, st);
-        bhalf_load<NT>(a, 0, n0, 0, S < nsteps(0) ? S : nsteps(0), bs);
-        stage_store(lds, a.ch_w[0] >> 3, st);
-        bhalf_store<NT>(bbuf, S < nsteps(0) ? S : nsteps(0), bs);
-        __syncthreads();
-        for (int c = 0; c < a.nchunk; ++c) {
-            const int nst = nsteps(c), nsg = (nst + S - 1) / S;
-            const bool more = c + 1 < a.nchunk;
-            for (int sg = 0; sg < nsg; ++sg) {  // one compute call site: one inlined copy of the step loop
-                const bool last = sg + 1 == nsg;
-                const int s0 = sg * S, s1 = last ? nst : s0 + S;
-                if (!last) {                     // this chunk's next stage
-                    const int e = s1 + S < nst ? s1 + S : nst;
-                    bhalf_load<NT>(a, c, n0, s1, e - s1, bs);
-                } else if (more) {
-                    const int nn = nsteps(c + 1);
-                    stage_load(a, c + 1, tx0, ty0, st);
-                    bhalf_load<NT>(a, c + 1, n0, 0, S < nn ? S : nn, bs);
-                }
-                compute_chunk<NT, true>(a, c, lds, bbuf, acc, lane, X, Yb, n0, s0, s1);
-                __syncthreads();
-                if (!last) {
-                    const int e = s1 + S < nst ? s1 + S : nst;
-                    bhalf_store<NT>(bbuf, e - s1, bs);
-                    __syncthreads();
-                }
-            }
-            if (more) {
+    // single halo and B buffers; per stage: the next stage's loads, this stage's MFMAs, two barriers around
+    // the LDS writes
+    constexpr int S = BStage<NT>::steps;
+    uint4 st[kStageRegs], bs[BStage<NT>::kRegs];
+    auto nsteps = [&](int c) { return a.ch_w[c] == 32 ? 9 : 5; };
+    stage_load(a, 0, tx0, ty0, st);
+    bstage_load<NT>(a, 0, n0, 0, S < nsteps(0) ? S : nsteps(0), bs);
+    stage_store(lds, a.ch_w[0] >> 3, st);
+    bstage_store<NT>(bbuf, S < nsteps(0) ? S : nsteps(0), bs);
+    __syncthreads();
+    for (int c = 0; c < a.nchunk; ++c) {
+        const int nst = nsteps(c), nsg = (nst + S - 1) / S;
+        const bool more = c + 1 < a.nchunk;
+        for (int sg = 0; sg < nsg; ++sg) {      // one compute call site: one inlined copy of the step loop
+            const bool last = sg + 1 == nsg;
+            const int s0 = sg * S, s1 = last ? nst : s0 + S;
+            if (!last) {                         // this chunk's next stage
+                const int e = s1 + S < nst ? s1 + S : nst;
+                bstage_load<NT>(a, c, n0, s1, e - s1, bs);
+            } else if (more) {
                 const int nn = nsteps(c + 1);
-                stage_store(lds, a.ch_w[c + 1] >> 3, st);
-                bhalf_store<NT>(bbuf, S < nn ? S : nn, bs);
+                stage_load(a, c + 1, tx0, ty0, st);
+                bstage_load<NT>(a, c + 1, n0, 0, S < nn ? S : nn, bs);
+            }
+            compute_chunk<NT>(a, c, lds, bbuf, acc, lane, X, Yb, s0, s1);
+            __syncthreads();
+            if (!last) {
+                const int e = s1 + S < nst ? s1 + S : nst;
+                bstage_store<NT>(bbuf, e - s1, bs);
                 __syncthreads();
             }
         }
-    } else {                                   // double-buffered halo, per-wave global B
-        stage_load(a, 0, tx0, ty0, st);
-        stage_store(lds, a.ch_w[0] >> 3, st);
-        __syncthreads();
-        for (int c = 0; c < a.nchunk; ++c) {
-            const bool more = c + 1 < a.nchunk;
-            if (more) stage_load(a, c + 1, tx0, ty0, st);      // in flight during the MFMAs
-            compute_chunk<NT, false>(a, c, lds + (c & 1) * kChunkBytes, nullptr, acc, lane, X, Yb, n0);
-            if (more) stage_store(lds + ((c + 1) & 1) * kChunkBytes, a.ch_w[c + 1] >> 3, st);
+        if (more) {
+            const int nn = nsteps(c + 1);
+            stage_store(lds, a.ch_w[c + 1] >> 3, st);
+            bstage_store<NT>(bbuf, S < nn ? S : nn, bs);
             __syncthreads();
         }
     }
 
-    // epilogue.  C/D: lane holds column co = 16 n + i and rows 4 h + r (r = register): pixel
-    // (2 h + (r & 1), r >> 1) of the group's 8x2 block -- one 2x2 quad per lane
-    // LDS out images: pixel pitch CS + 8 halves (16 B more than the channels; float images 17 floats) so
-    // the 4 quads of a wave-instruction's scattered 2-B / 4-B writes fall on different banks
-    if constexpr (POST == POST_STORE) {
-        constexpr int CS = NT * 16, CP = CS + 8;
+    // epilogue: the tile's LDS image (tile_image; POST_FINAL: floats at a pitch of 17), then copied out
+    if constexpr (POST != POST_FINAL) {
+        constexpr bool pool = POST == POST_POOL;
+        constexpr int OW = pool ? kTile / 2 : kTile, NPX = OW * OW;
+        constexpr int CP = NT * 16 + 8, PPP = NT * 2;          // pixel pitch (halves), 16-B pieces per pixel
         _Float16* o = (_Float16*)lds;
+        float bv[NT];
 #pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            const float bv = a.bias[16 * (n0 + n) + i];
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float v = acc[g][n][r] + bv;
-                    if (RELU) v = v > 0.0f ? v : 0.0f;
-                    const int px = (8 * wy + 2 * g + (r >> 1)) * kTile + 8 * wx + 2 * h + (r & 1);
-                    o[px * CP + 16 * n + i] = (_Float16)v;
-                }
-        }
+        for (int n = 0; n < NT; ++n) bv[n] = a.bias[16 * (n0 + n) + i];
+        tile_image<NT, POST, OW>(o, acc, bv, wy, wx, h, i);
         __syncthreads();
-        constexpr int PPP = CS / 8;            // 16-B pieces per pixel
-        for (int q = threadIdx.x; q < 256 * PPP; q += 256) {
+        const int oh = pool ? a.h >> 1 : a.h, ow = pool ? a.w_ >> 1 : a.w_;
+        const int oy0 = pool ? ty0 >> 1 : ty0, ox0 = pool ? tx0 >> 1 : tx0;
+        for (int q = threadIdx.x; q < NPX * PPP; q += 256) {
             const int px = q / PPP, pc = q - px * PPP;
-            const int gy = ty0 + (px >> 4), gx = tx0 + (px & 15);
-            if (gy < a.h && gx < a.w_)
-                *(uint4*)(a.dst + ((size_t)(gy + 1) * (size_t)(a.w_ + 2) + (size_t)(gx + 1)) * a.dcs + 16 * n0 + 8 * pc) =
+            const int gy = oy0 + px / OW, gx = ox0 + px % OW;
+            if (gy < oh && gx < ow)
+                *(uint4*)(a.dst + ((size_t)(gy + 1) * (size_t)(ow + 2) + (size_t)(gx + 1)) * a.dcs + 16 * n0 + 8 * pc) =
                     *(const uint4*)(o + px * CP + 8 * pc);
         }
-    } else if constexpr (POST == POST_POOL) {
-        constexpr int CS = NT * 16, CP = CS + 8;
-        _Float16* o = (_Float16*)lds;
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            const float bv = a.bias[16 * (n0 + n) + i];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 v4 = acc[g][n];
-                float m = fmaxf(fmaxf(v4[0], v4[1]), fmaxf(v4[2], v4[3])) + bv;
-                if (RELU) m = m > 0.0f ? m : 0.0f;
-                const int px = (4 * wy + g) * 8 + 4 * wx + h;   // 8x8 pooled tile
-                o[px * CP + 16 * n + i] = (_Float16)m;
-            }
-        }
-        __syncthreads();
-        constexpr int PPP = CS / 8;
-        const int ph = a.h >> 1, pw = a.w_ >> 1;
-        for (int q = threadIdx.x; q < 64 * PPP; q += 256) {
-            const int px = q / PPP, pc = q - px * PPP;
-            const int gy = (ty0 >> 1) + (px >> 3), gx = (tx0 >> 1) + (px & 7);
-            if (gy < ph && gx < pw)
-                *(uint4*)(a.dst + ((size_t)(gy + 1) * (size_t)(pw + 2) + (size_t)(gx + 1)) * a.dcs + 16 * n0 + 8 * pc) =
-                    *(const uint4*)(o + px * CP + 8 * pc);
-        }
-    } else {   // POST_FINAL: dec_conv0 (linear) + the output transform, float3 at the caller's stride
+    } else {   // dec_conv0 (linear) + the output transform, float3 at the caller's stride
         float* o = (float*)lds;
         const float bv = a.bias[i];
 #pragma unroll
@@ -536,15 +461,7 @@ __device__ __forceinline__ void pstage_compute(const ConvArgs& a, int c, const u
         const uint8_t* ab = buf + Yb * kPPitch32 + X * 64 + h * 16;
         for (int st = 0; st < 9; ++st) {
             const int ky = st / 3, kx = st - 3 * ky;
-            half8 b[NT];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) b[n] = bp[(st * NT + n) * 64];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const half8 av = *(const half8*)(ab + (2 * g + ky) * kPPitch32 + kx * 64);
-#pragma unroll
-                for (int n = 0; n < NT; ++n) acc[g][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, b[n], acc[g][n], 0, 0, 0);
-            }
+            kstep<NT>(acc, ab + ky * kPPitch32 + kx * 64, kPPitch32, bp + st * NT * 64);
         }
     } else {
         const uint8_t* ab = buf + Yb * kPPitch16 + X * 32 + (h & 1) * 16;
@@ -552,15 +469,7 @@ __device__ __forceinline__ void pstage_compute(const ConvArgs& a, int c, const u
             int tap = 2 * st + (h >> 1);
             tap = tap > 8 ? 8 : tap;                   // tap 9: zero weights
             const int ky = tap / 3, kx = tap - 3 * ky;
-            half8 b[NT];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) b[n] = bp[(st * NT + n) * 64];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const half8 av = *(const half8*)(ab + (2 * g + ky) * kPPitch16 + kx * 32);
-#pragma unroll
-                for (int n = 0; n < NT; ++n) acc[g][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, b[n], acc[g][n], 0, 0, 0);
-            }
+            kstep<NT>(acc, ab + ky * kPPitch16 + kx * 32, kPPitch16, bp + st * NT * 64);
         }
     }
 }
@@ -576,7 +485,7 @@ __device__ __forceinline__ void lds_barrier() {
     raw_barrier();
 }
 
-template <int NT, int POST, bool RELU>
+template <int NT, int POST>
 __global__ void __launch_bounds__(kPThreads) k_conv3p(ConvArgs a) {
     using C = PCfg<NT>;
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * C::kBuf];
@@ -621,25 +530,11 @@ __global__ void __launch_bounds__(kPThreads) k_conv3p(ConvArgs a) {
             constexpr int OW = pool ? kPTW / 2 : kPTW, NPX = pool ? kPTH * kPTW / 4 : kPTH * kPTW;
             _Float16* o = (_Float16*)buf;
             lds_barrier();                             // every wave's MFMAs have read the stage
+            tile_image<NT, POST, OW>(o, acc, bv, wy, wx, h, i);
 #pragma unroll
-            for (int n = 0; n < NT; ++n)
+            for (int g = 0; g < 4; ++g)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    if constexpr (pool) {
-                        const f32x4 v4 = acc[g][n];
-                        float m = fmaxf(fmaxf(v4[0], v4[1]), fmaxf(v4[2], v4[3])) + bv[n];
-                        if (RELU) m = m > 0.0f ? m : 0.0f;
-                        o[((4 * wy + g) * OW + 4 * wx + h) * CP + 16 * n + i] = (_Float16)m;
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float v = acc[g][n][r] + bv[n];
-                            if (RELU) v = v > 0.0f ? v : 0.0f;
-                            o[((8 * wy + 2 * g + (r >> 1)) * OW + 8 * wx + 2 * h + (r & 1)) * CP + 16 * n + i] = (_Float16)v;
-                        }
-                    }
-                    acc[g][n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-                }
+                for (int n = 0; n < NT; ++n) acc[g][n] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
             lds_barrier();
             // the image's LDS reads in asm: before a compiler-visible ds_read the compiler waits vmcnt(0) --
             // for the next stage's DMA and for every store issued before it
@@ -825,24 +720,24 @@ static bool parse_tza(const uint8_t* p, size_t n, std::map<std::string, Tensor>&
 }
 
 enum BufId { B_IN, B_E0, B_P1, B_P2, B_P3, B_P4, B_E5A, B_E5B, B_D4A, B_D4B, B_D3A, B_D3B, B_D2A, B_D2B, B_D1A, B_D1B, B_COUNT };
-struct LayerDef { const char* name; int src0, up0, src1, level, post, relu, dst; };
+struct LayerDef { const char* name; int src0, up0, src1, level, post, dst; };
 static const LayerDef kNet[16] = {
-    {"enc_conv0", B_IN, 0, -1, 0, POST_STORE, 1, B_E0},
-    {"enc_conv1", B_E0, 0, -1, 0, POST_POOL, 1, B_P1},
-    {"enc_conv2", B_P1, 0, -1, 1, POST_POOL, 1, B_P2},
-    {"enc_conv3", B_P2, 0, -1, 2, POST_POOL, 1, B_P3},
-    {"enc_conv4", B_P3, 0, -1, 3, POST_POOL, 1, B_P4},
-    {"enc_conv5a", B_P4, 0, -1, 4, POST_STORE, 1, B_E5A},
-    {"enc_conv5b", B_E5A, 0, -1, 4, POST_STORE, 1, B_E5B},
-    {"dec_conv4a", B_E5B, 1, B_P3, 3, POST_STORE, 1, B_D4A},
-    {"dec_conv4b", B_D4A, 0, -1, 3, POST_STORE, 1, B_D4B},
-    {"dec_conv3a", B_D4B, 1, B_P2, 2, POST_STORE, 1, B_D3A},
-    {"dec_conv3b", B_D3A, 0, -1, 2, POST_STORE, 1, B_D3B},
-    {"dec_conv2a", B_D3B, 1, B_P1, 1, POST_STORE, 1, B_D2A},
-    {"dec_conv2b", B_D2A, 0, -1, 1, POST_STORE, 1, B_D2B},
-    {"dec_conv1a", B_D2B, 1, B_IN, 0, POST_STORE, 1, B_D1A},
-    {"dec_conv1b", B_D1A, 0, -1, 0, POST_STORE, 1, B_D1B},
-    {"dec_conv0", B_D1B, 0, -1, 0, POST_FINAL, 0, -1},
+    {"enc_conv0", B_IN, 0, -1, 0, POST_STORE, B_E0},
+    {"enc_conv1", B_E0, 0, -1, 0, POST_POOL, B_P1},
+    {"enc_conv2", B_P1, 0, -1, 1, POST_POOL, B_P2},
+    {"enc_conv3", B_P2, 0, -1, 2, POST_POOL, B_P3},
+    {"enc_conv4", B_P3, 0, -1, 3, POST_POOL, B_P4},
+    {"enc_conv5a", B_P4, 0, -1, 4, POST_STORE, B_E5A},
+    {"enc_conv5b", B_E5A, 0, -1, 4, POST_STORE, B_E5B},
+    {"dec_conv4a", B_E5B, 1, B_P3, 3, POST_STORE, B_D4A},
+    {"dec_conv4b", B_D4A, 0, -1, 3, POST_STORE, B_D4B},
+    {"dec_conv3a", B_D4B, 1, B_P2, 2, POST_STORE, B_D3A},
+    {"dec_conv3b", B_D3A, 0, -1, 2, POST_STORE, B_D3B},
+    {"dec_conv2a", B_D3B, 1, B_P1, 1, POST_STORE, B_D2A},
+    {"dec_conv2b", B_D2A, 0, -1, 1, POST_STORE, B_D2B},
+    {"dec_conv1a", B_D2B, 1, B_IN, 0, POST_STORE, B_D1A},
+    {"dec_conv1b", B_D1A, 0, -1, 0, POST_STORE, B_D1B},
+    {"dec_conv0", B_D1B, 0, -1, 0, POST_FINAL, -1},
 };
 
 struct Chunk { int src, base, w, step; };
@@ -974,6 +869,7 @@ struct rs_denoiser {
     uint32_t pipe = 0u;                         // layers (bit l) on k_conv3p where it applies (2..4 n-tiles):
                                                 // RESTIR_DN_PIPE=<mask> or 1 (all); measured slower, off
     int cus = 256;                              // its workgroups (RESTIR_DN_PIPE_GRID caps them: tests)
+    size_t fill = kFillWorkgroups;              // RESTIR_DN_FILL: a layer with fewer workgroups splits its channels
 };
 
 namespace {
@@ -1009,41 +905,66 @@ int ensure_bufs(rs_denoiser* d, int H, int W, hipStream_t st) {
     return RS_OK;
 }
 
-template <int NT, int POST, bool RELU>
-void launch(const ConvArgs& a, dim3 g, hipStream_t st) { k_conv3<NT, POST, RELU><<<g, 256, 0, st>>>(a); }
-
-bool dispatch(int nt, int post, bool relu, const ConvArgs& a, dim3 g, hipStream_t st) {
-#define RS_DN_CASE(N)                                                       \
-    case N:                                                                 \
-        if (post == POST_POOL) launch<N, POST_POOL, true>(a, g, st);        \
-        else if (relu) launch<N, POST_STORE, true>(a, g, st);              \
-        else launch<N, POST_STORE, false>(a, g, st);                       \
-        return true;
+// a workgroup's n-tiles and a layer's epilogue as compile-time constants: the only switch over (nt, post).
+// Calls f(NT, POST) and returns true, or returns false for a pair no kernel is built for (POST_FINAL has
+// one n-tile)
+template <int V> using Const = std::integral_constant<int, V>;
+template <class Fn>
+bool with_conv(int nt, int post, Fn&& f) {
     if (post == POST_FINAL) {
-        if (nt != 1) return false;
-        launch<1, POST_FINAL, false>(a, g, st);
-        return true;
+        if (nt == 1) f(Const<1>{}, Const<POST_FINAL>{});
+        return nt == 1;
     }
+    auto g = [&](auto N) {
+        if (post == POST_POOL) f(N, Const<POST_POOL>{});
+        else f(N, Const<POST_STORE>{});
+        return true;
+    };
     switch (nt) {
-        RS_DN_CASE(1) RS_DN_CASE(2) RS_DN_CASE(3) RS_DN_CASE(4)
+        case 1: return g(Const<1>{});
+        case 2: return g(Const<2>{});
+        case 3: return g(Const<3>{});
+        case 4: return g(Const<4>{});
         default: return false;
     }
-#undef RS_DN_CASE
 }
 
-bool dispatch_pipe(int nt, int post, bool relu, const ConvArgs& a, dim3 g, hipStream_t st) {
-#define RS_DNP_CASE(N)                                                                          \
-    case N:                                                                                     \
-        if (post == POST_POOL) k_conv3p<N, POST_POOL, true><<<g, kPThreads, 0, st>>>(a);        \
-        else if (relu) k_conv3p<N, POST_STORE, true><<<g, kPThreads, 0, st>>>(a);              \
-        else k_conv3p<N, POST_STORE, false><<<g, kPThreads, 0, st>>>(a);                       \
-        return true;
-    if (post == POST_POOL && !relu) return false;
-    switch (nt) {
-        RS_DNP_CASE(2) RS_DNP_CASE(3) RS_DNP_CASE(4)
-        default: return false;
+// layer l's kernel arguments at the current image size; `out`: the caller's H x W image, `ost` floats per pixel
+ConvArgs conv_args(const rs_denoiser* d, int l, float* out, int ost, int H, int W) {
+    const LayerDef& ld = kNet[l];
+    const Layer& L = d->L[l];
+    ConvArgs a{};
+    const int srcs[2] = {ld.src0, ld.src1};
+    for (int s = 0; s < 2; ++s) {
+        if (srcs[s] < 0) continue;
+        const int lv = d->net.buflev[srcs[s]];
+        a.src[s] = d->buf[srcs[s]];
+        a.cs[s] = d->net.bufcs[srcs[s]];
+        a.sh[s] = d->Hp >> lv;
+        a.sw[s] = d->Wp >> lv;
+        a.up[s] = s == 0 ? ld.up0 : 0;
     }
-#undef RS_DNP_CASE
+    a.nchunk = (int)L.chunks.size();
+    for (int c = 0; c < a.nchunk; ++c) {
+        a.ch_src[c] = L.chunks[c].src; a.ch_base[c] = L.chunks[c].base;
+        a.ch_w[c] = L.chunks[c].w; a.ch_step[c] = L.chunks[c].step;
+    }
+    a.w = L.dw; a.bias = L.db; a.nt_total = L.nt;
+    a.h = d->Hp >> ld.level; a.w_ = d->Wp >> ld.level;
+    if (ld.post != POST_FINAL) { a.dst = d->buf[ld.dst]; a.dcs = d->net.bufcs[ld.dst]; }
+    else {
+        a.out = out; a.ostride = ost; a.H = H; a.W = W; a.scale = d->d_scale;
+        a.inv_norm = pu_forward(HDR_Y_MAX);
+    }
+    return a;
+}
+
+void fill_info(const Net& net, rs_denoiser_info* info) {
+    std::memset(info, 0, sizeof *info);
+    info->input_channels = net.ic;
+    for (int l = 0; l < 16; ++l) info->channels[l] = net.co[l];
+    info->parameters = net.params;
+    info->mac_per_pixel = net.mac_per_px;
 }
 
 int create_impl(rs_context* ctx, const void* tza, size_t bytes, rs_denoiser** out) {
@@ -1058,6 +979,7 @@ int create_impl(rs_context* ctx, const void* tza, size_t bytes, rs_denoiser** ou
     if (const char* e = std::getenv("RESTIR_DN_PIPE")) d->pipe = std::strcmp(e, "1") == 0 ? 0xffffu : (uint32_t)std::strtoul(e, nullptr, 0);
     if (hipDeviceGetAttribute(&d->cus, hipDeviceAttributeMultiprocessorCount, d->device) != hipSuccess || d->cus < 1) d->cus = 256;
     if (const char* e = std::getenv("RESTIR_DN_PIPE_GRID")) d->cus = std::max(1, std::atoi(e));
+    if (const char* e = std::getenv("RESTIR_DN_FILL")) d->fill = (size_t)std::max(1, std::atoi(e));
     if (!check_net(T, d->net, err)) { delete d; return rs::ctx_fail(ctx, RS_E_INVALID, "rs_denoiser_create: " + err); }
     (void)hipGetLastError();
     if (hipSetDevice(rs::ctx_device(ctx)) != hipSuccess) { delete d; return rs::ctx_fail(ctx, RS_E_HIP, "rs_denoiser_create: hipSetDevice"); }
@@ -1117,49 +1039,27 @@ int denoise_run(rs_denoiser* d, hipStream_t st, const float* color, int cst, con
     for (int l = 0; l < 16; ++l) {
         const LayerDef& ld = kNet[l];
         const Layer& L = d->L[l];
-        ConvArgs a{};
-        const int srcs[2] = {ld.src0, ld.src1};
-        for (int s = 0; s < 2; ++s) {
-            if (srcs[s] < 0) continue;
-            const int lv = d->net.buflev[srcs[s]];
-            a.src[s] = d->buf[srcs[s]];
-            a.cs[s] = d->net.bufcs[srcs[s]];
-            a.sh[s] = d->Hp >> lv;
-            a.sw[s] = d->Wp >> lv;
-            a.up[s] = s == 0 ? ld.up0 : 0;
-        }
-        a.nchunk = (int)L.chunks.size();
-        for (int c = 0; c < a.nchunk; ++c) {
-            a.ch_src[c] = L.chunks[c].src; a.ch_base[c] = L.chunks[c].base;
-            a.ch_w[c] = L.chunks[c].w; a.ch_step[c] = L.chunks[c].step;
-        }
-        a.w = L.dw; a.bias = L.db;
-        a.h = d->Hp >> ld.level; a.w_ = d->Wp >> ld.level;
-        if (ld.post != POST_FINAL) { a.dst = d->buf[ld.dst]; a.dcs = d->net.bufcs[ld.dst]; }
-        else {
-            a.out = out; a.ostride = ost; a.H = H; a.W = W; a.scale = d->d_scale;
-            a.inv_norm = pu_forward(HDR_Y_MAX);
-        }
-        a.nt_total = L.nt;
+        const ConvArgs a = conv_args(d, l, out, ost, H, W);
+        bool ok;
         if (((d->pipe >> l) & 1u) && ld.post != POST_FINAL && L.nt >= 2 && L.nt <= 4) {
             // one persistent workgroup per CU over 16 x 32 tiles (or one per tile when there are fewer)
             const size_t nt = (size_t)((a.w_ + kPTW - 1) / kPTW) * (size_t)((a.h + kPTH - 1) / kPTH);
             const dim3 g((unsigned)std::min<size_t>(nt, (size_t)d->cus));
-            if (!dispatch_pipe(L.nt, ld.post, ld.relu != 0, a, g, st)) return dfail(d, RS_E_UNSUPPORTED, "rs_denoise: unsupported layer");
-            DCHK(d, hipGetLastError());
-            if (d->timed) DCHK(d, hipEventRecord(d->evl[l + 1], st));
-            continue;
+            ok = with_conv(L.nt, ld.post, [&](auto N, auto P) {     // built for the pairs the condition above admits
+                if constexpr (N() >= 2 && P() != POST_FINAL) k_conv3p<N(), P()><<<g, kPThreads, 0, st>>>(a);
+            });
+        } else {
+            // n-tiles per workgroup: all of them, unless the layer's tiles cannot fill the chip (the coarse
+            // levels): then the output channels split over blockIdx.z (each split re-stages the input halo)
+            const unsigned gx = (unsigned)((a.w_ + kTile - 1) / kTile), gy = (unsigned)((a.h + kTile - 1) / kTile);
+            int ntw = 1;
+            if (ld.post != POST_FINAL)
+                for (int k = L.nt < kMaxNtw ? L.nt : kMaxNtw; k >= 1; --k)
+                    if (L.nt % k == 0) { ntw = k; if ((size_t)gx * gy * (L.nt / k) >= d->fill) break; }
+            const dim3 g(gx, gy, (unsigned)(L.nt / ntw));
+            ok = with_conv(ntw, ld.post, [&](auto N, auto P) { k_conv3<N(), P()><<<g, 256, 0, st>>>(a); });
         }
-        // n-tiles per workgroup: all of them, unless the layer's tiles cannot fill the chip (the coarse
-        // levels): then the output channels split over blockIdx.z (each split re-stages the input halo)
-        const unsigned gx = (unsigned)((a.w_ + kTile - 1) / kTile), gy = (unsigned)((a.h + kTile - 1) / kTile);
-        a.nt_total = L.nt;
-        int ntw = 1;
-        if (ld.post != POST_FINAL)
-            for (int k = L.nt < kMaxNtw ? L.nt : kMaxNtw; k >= 1; --k)
-                if (L.nt % k == 0) { ntw = k; if ((size_t)gx * gy * (L.nt / k) >= kFillWorkgroups) break; }
-        const dim3 g(gx, gy, (unsigned)(L.nt / ntw));
-        if (!dispatch(ntw, ld.post, ld.relu != 0, a, g, st)) return dfail(d, RS_E_UNSUPPORTED, "rs_denoise: unsupported layer width");
+        if (!ok) return dfail(d, RS_E_UNSUPPORTED, "rs_denoise: unsupported layer width");
         DCHK(d, hipGetLastError());
         if (d->timed) DCHK(d, hipEventRecord(d->evl[l + 1], st));
     }
@@ -1176,13 +1076,7 @@ extern "C" int rs_denoiser_check_weights(const void* tza, size_t bytes, rs_denoi
     Net net;
     if (!parse_tza((const uint8_t*)tza, bytes, T, err) || !check_net(T, net, err))
         return rs::ctx_fail(nullptr, RS_E_INVALID, "rs_denoiser_check_weights: " + err);
-    if (info) {
-        std::memset(info, 0, sizeof *info);
-        info->input_channels = net.ic;
-        for (int l = 0; l < 16; ++l) info->channels[l] = net.co[l];
-        info->parameters = net.params;
-        info->mac_per_pixel = net.mac_per_px;
-    }
+    if (info) fill_info(net, info);
     return RS_OK;
 }
 
@@ -1204,11 +1098,7 @@ extern "C" int rs_denoiser_create_from_file(rs_context* ctx, const char* path, r
 
 extern "C" int rs_denoiser_info_get(const rs_denoiser* d, rs_denoiser_info* info) {
     if (!d || !info) return rs::ctx_fail(d ? d->ctx : nullptr, RS_E_INVALID, "rs_denoiser_info_get: null argument");
-    std::memset(info, 0, sizeof *info);
-    info->input_channels = d->net.ic;
-    for (int l = 0; l < 16; ++l) info->channels[l] = d->net.co[l];
-    info->parameters = d->net.params;
-    info->mac_per_pixel = d->net.mac_per_px;
+    fill_info(d->net, info);
     return RS_OK;
 }
 

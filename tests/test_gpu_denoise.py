@@ -8,7 +8,9 @@ Two levels:
     float16 rounding boundary: every element within 1 float16 ulp + 3e-5 x (sum of |w x| + |b|, the scale of
     a float32 accumulation's rounding error over <= 1440 terms), at most 2 % of them different at all; zero
     borders and zero channel padding checked too; the last layer's float32 output (with the inverse
-    transfer function) within 2e-4 relative of the float64 result;
+    transfer function) within 2e-4 relative of the float64 result; run with the default grouping of a layer's
+    n-tiles into workgroups and with RESTIR_DN_FILL=1 (up to 4 per workgroup), whose tensors must also be
+    bit-identical to each other (test_channel_split_bit_identical);
   * end to end vs the fp32 reference with float16 storage (`quantize=True`): in the network-output (PU)
     domain mean |err| <= 1e-3, max <= 2e-2.  With float16 storage the result depends on the accumulation
     order: two exact-storage references that differ only in float32 vs float64 accumulation already differ
@@ -79,14 +81,25 @@ def test_denoise_matches_reference(ctx, H, W):
     assert mq <= 1e-3 and xq <= 2e-2, (mq, xq)
 
 
-@pytest.mark.parametrize("H,W", [(48, 64), (37, 83)])
-def test_every_layer_matches_float64(ctx, H, W):
+@pytest.mark.parametrize("H,W,fill", [pytest.param(H, W, fill, id=f"{H}-{W}" + ("-fill" + fill if fill else ""))
+                                      for H, W in ((48, 64), (37, 83)) for fill in (None, "1")])
+def test_every_layer_matches_float64(ctx, monkeypatch, H, W, fill):
+    """fill = "1" (RESTIR_DN_FILL): no layer splits its output channels over workgroups, so each runs with the
+    largest n-tile count <= 4 that divides its n-tiles -- k_conv3 with 1, 2, 3 and 4 n-tiles, storing and
+    pooling, where the default at these sizes runs nearly every layer with 1."""
     r, d, w = ctx
     color, albedo, normal = _images(H, W, seed=31 + H)
-    got = _run(d, color, albedo, normal, scale=0.9)
+    if fill is not None:
+        monkeypatch.setenv("RESTIR_DN_FILL", fill)
+        d = Denoiser(r, w)
+    try:
+        got = _run(d, color, albedo, normal, scale=0.9)
+        dumps = [d.dump(i) for i in range(16)]
+    finally:
+        if fill is not None:
+            d.close()
     t = {}
-    for i in range(16):
-        a, real = d.dump(i)
+    for i, (a, real) in enumerate(dumps):
         assert not a[0].any() and not a[-1].any() and not a[:, 0].any() and not a[:, -1].any(), f"tensor {i}: border"
         assert not a[..., real:].any(), f"tensor {i}: channel padding"
         t[i] = a[1:-1, 1:-1, :real].astype(np.float64).transpose(2, 0, 1)
@@ -110,6 +123,27 @@ def test_every_layer_matches_float64(ctx, H, W):
         print(f"{name}: {off.mean() * 100:.3f} % of {diff.size} elements differ, max {float((diff / bound).max()):.3f} of the bound")
         assert (diff <= bound).all(), (name, float((diff / bound).max()))
         assert off.mean() <= 0.02, (name, float(off.mean()))
+
+
+def test_channel_split_bit_identical(ctx, monkeypatch):
+    """However a layer's n-tiles are grouped into workgroups (RESTIR_DN_FILL=1: up to 4 per workgroup; the default
+    at this size: mostly 1), each n-tile's accumulators see the same k-steps in the same order: every tensor and
+    the output are bit-identical."""
+    r, d, w = ctx
+    H, W = 37, 83
+    color, albedo, normal = _images(H, W, seed=13)
+    o0 = _run(d, color, albedo, normal, scale=0.8)
+    t0 = [d.dump(i)[0] for i in range(16)]
+    monkeypatch.setenv("RESTIR_DN_FILL", "1")
+    d1 = Denoiser(r, w)
+    try:
+        o1 = _run(d1, color, albedo, normal, scale=0.8)
+        t1 = [d1.dump(i)[0] for i in range(16)]
+    finally:
+        d1.close()
+    for i in range(16):
+        assert np.array_equal(t0[i].view(np.uint16), t1[i].view(np.uint16)), f"tensor {i}"
+    assert np.array_equal(o0, o1)
 
 
 @pytest.mark.parametrize("H,W,grid", [(48, 64, "2"), (37, 83, "3"), (540, 960, None), (1080, 1920, None)])
