@@ -125,13 +125,16 @@ public:
     // (pg/NEEPathIntegrator.cpp:72-131, MIS direct integrator): one frame of samplesPerPixel paths per pixel
     // under pathParams; frame_data() is this frame (the call waits for it), shadingPassDuration /
     // totalFrameDuration the launch.  The ReSTIR history is untouched; frameCtr keys the RNG and advances.
+    // unbiasedEstimator: rs_render_path_unbiased instead -- the textbook NEE + MIS estimator, which equals the
+    // light where the reference's is dark (materials with Kd and Ks); params.normal_offset is not used by it.
     void produceStandard(float t = 0.0f) {
         (void)t;
         if (!scene_) throw Error(RS_E_INVALID, "produceStandard: no scene loaded");
         finish();
         rs_pass_times pt{};
-        check(rs_render_path(ctx_, scene_, &camera_, &params, &pathParams, frameCtr, samplesPerPixel, ring_[cur_],
-                             timePasses ? &pt : nullptr), ctx_);
+        check((unbiasedEstimator ? rs_render_path_unbiased : rs_render_path)(
+                  ctx_, scene_, &camera_, &params, &pathParams, frameCtr, samplesPerPixel, ring_[cur_],
+                  timePasses ? &pt : nullptr), ctx_);
         shown_ = ring_[cur_]; shown_frame_ = (long long)frameCtr;
         cur_ = (cur_ + 1) % kRing;
         if (timePasses) {
@@ -186,6 +189,7 @@ public:
     // produceStandard: RenderParams::maxBounceCount, NaivePathIntegrator::RR, NEEPathIntegrator::calcDI / calcGI
     rs_path_params pathParams{5, 1, 1, 1};
     uint32_t samplesPerPixel = 1;
+    bool unbiasedEstimator{false};          // produceStandard: the unbiased estimator instead of the reference's
     uint32_t frameCtr = 0;
     int pipelineDepth = 0;
     bool timePasses = true;

@@ -237,6 +237,18 @@ typedef struct {
 int rs_render_path(rs_context* ctx, const rs_scene* scene, const rs_camera* camera,
                    const rs_frame_params* params, const rs_path_params* path, uint32_t frame_index,
                    uint32_t spp, float* frame_rgb_host, rs_pass_times* times);
+/* ---- Unbiased NEE + MIS path tracer: the ground truth that equals the light --------------------- */
+/* rs_render_direct_mis and rs_render_path restate the reference's estimators, which are dark on a material with
+ * both Kd and Ks (0.59 of the furnace value at shininess 1), high by about normal_offset / (t cos theta) on the
+ * BRDF part, and dark past bounce 5 under roulette.  This entry is the textbook estimator over the same material
+ * model: per vertex one light sample and one BRDF sample of the full BRDF over the mixture pdf, whose ray --
+ * started at the surface point, where the shadow rays start -- both finds the emitters (power heuristic) and
+ * carries the path on; Russian roulette (bounce > 5, q = min(max(Kd, Ks) component, 1)) divides the whole
+ * return of the vertex.  params->normal_offset is not used.  With path->calc_gi = 0 it is the unbiased
+ * direct-light ground truth.  Contract, error codes and ranges of rs_render_path; rs_path_params as above. */
+int rs_render_path_unbiased(rs_context* ctx, const rs_scene* scene, const rs_camera* camera,
+                            const rs_frame_params* params, const rs_path_params* path, uint32_t frame_index,
+                            uint32_t spp, float* frame_rgb_host, rs_pass_times* times);
 
 /* Pass times and rays summed over every frame finished since context creation (or the last reset),
  * without a host sync per frame: each frame records into its own slot of an event ring and the rays

@@ -7,6 +7,7 @@
 #include "rs_passes.h"
 #include "rs_mis.h"
 #include "rs_path.h"
+#include "rs_path_unbiased.h"
 #include "rs_post.h"
 #include "rs_refit.h"
 #include "../../include/restir_c.h"
@@ -2041,26 +2042,46 @@ extern "C" int rs_render_direct_mis(rs_context* c, const rs_scene* s, const rs_c
     });
 }
 
-// NEE path tracer: the global-illumination ground truth (rs_path.h).  The vertex records of the paths in flight
-// take (max_bounces + 1) * 8 KiB of dynamic LDS per workgroup: 48 KiB at the default, 128 KiB at the cap.
-extern "C" int rs_render_path(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
-                              const rs_path_params* pp, uint32_t frame_index, uint32_t spp, float* frame_rgb_host,
-                              rs_pass_times* t) {
-    if (!pp) return fail(c, RS_E_INVALID, "rs_render_path: null argument");
+// The two path tracers: rs_render_path's checks, record array and launch, said once.  The vertex records of the
+// paths in flight take (max_bounces + 1) * 8 KiB of dynamic LDS per workgroup: 48 KiB at the default, 128 KiB at the
+// cap.  kernel(T) is the instantiation for traversal kind T; the LDS attribute is that kernel's own.
+template <class Kernel>
+static int render_path_with(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                            const rs_path_params* pp, uint32_t frame_index, uint32_t spp, float* frame_rgb_host,
+                            rs_pass_times* t, const char* who, Kernel&& kernel) {
+    const std::string fn = who;
+    if (!pp) return fail(c, RS_E_INVALID, fn + ": null argument");
     if (pp->max_bounces < 0 || pp->max_bounces > 15)
-        return fail(c, RS_E_INVALID, "rs_render_path: max_bounces must be in [0, 15]");
+        return fail(c, RS_E_INVALID, fn + ": max_bounces must be in [0, 15]");
     const PathConst Q = {(int)spp, pp->max_bounces, pp->russian_roulette ? 1 : 0, pp->calc_di ? 1 : 0, pp->calc_gi ? 1 : 0};
     const size_t lds = (size_t)(Q.max_bounces + 1) * kPathRec * kPathBlock * sizeof(float);
-    return render_ground_truth(c, s, cam, P, frame_index, spp, frame_rgb_host, t, "rs_render_path",
+    return render_ground_truth(c, s, cam, P, frame_index, spp, frame_rgb_host, t, who,
                                [&](auto T, const DevScene& S, const FrameConst& F, dim3 g, CountSlot slot) {
+        const auto k = kernel(T);
         if (lds > 64 * 1024) {       // beyond what a launch may ask for unannounced
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_path_nee<T()>),
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
         }
-        k_path_nee<T()><<<g, kPathBlock, lds, c->fr.fs>>>(S, F, Q, c->lane().fb, slot);
+        k<<<g, kPathBlock, lds, c->fr.fs>>>(S, F, Q, c->lane().fb, slot);
         return hipGetLastError();
     });
+}
+
+// NEE path tracer: the global-illumination ground truth (rs_path.h), the reference's estimator
+extern "C" int rs_render_path(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                              const rs_path_params* pp, uint32_t frame_index, uint32_t spp, float* frame_rgb_host,
+                              rs_pass_times* t) {
+    return render_path_with(c, s, cam, P, pp, frame_index, spp, frame_rgb_host, t, "rs_render_path",
+                            [](auto T) { return &k_path_nee<T()>; });
+}
+
+// The unbiased NEE + MIS path tracer (rs_path_unbiased.h)
+extern "C" int rs_render_path_unbiased(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                                       const rs_path_params* pp, uint32_t frame_index, uint32_t spp,
+                                       float* frame_rgb_host, rs_pass_times* t) {
+    return render_path_with(c, s, cam, P, pp, frame_index, spp, frame_rgb_host, t, "rs_render_path_unbiased",
+                            [](auto T) { return &k_path_unbiased<T()>; });
 }
 
 extern "C" int rs_get_frame_device_ptr(rs_context* c, const float** dptr) {

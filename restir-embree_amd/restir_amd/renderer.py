@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = [
     "rs_denoiser_check_weights", "rs_denoiser_create", "rs_denoiser_create_from_file", "rs_denoiser_info_get",
     "rs_denoiser_execute", "rs_denoise_frame", "rs_context_set_denoiser", "rs_denoiser_set_timing",
     "rs_denoiser_last_ms", "rs_denoiser_layer_ms", "rs_denoiser_get_scale", "rs_denoiser_dump", "rs_denoiser_destroy",
-    "rs_render_path", "rs_debug_bvh_tree", "rs_debug_light_tables",
+    "rs_render_path", "rs_debug_bvh_tree", "rs_debug_light_tables", "rs_render_path_unbiased",
 ]
 
 # BVH traversal kinds (include/restir_c.h RS_TRAVERSAL_*)
@@ -210,6 +210,7 @@ def load_library(path: str = LIB_PATH):
                                        ctypes.POINTER(PassTimes)]
     L.rs_render_path.argtypes = [vp, vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(FrameParams),
                                  ctypes.POINTER(PathParams), u32, u32, fp, ctypes.POINTER(PassTimes)]
+    L.rs_render_path_unbiased.argtypes = L.rs_render_path.argtypes
     L.rs_frame_readback.argtypes = [vp, fp, ctypes.POINTER(ctypes.c_uint64)]
     L.rs_frame_wait.argtypes = [vp, ctypes.c_uint64]
     L.rs_host_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
@@ -624,10 +625,14 @@ class Renderer:
         return out
 
     def render_direct_mis(self, scene: Scene, camera, params: FrameParams, frame_index: int = 0, spp: int = 1,
-                          copy_out: bool = True, timed: bool = False) -> np.ndarray | None:
+                          copy_out: bool = True, timed: bool = False, unbiased: bool = False) -> np.ndarray | None:
         """MIS direct-light ground truth (rs_render_direct_mis; DirectMISIntegrator, calcGI off): spp
         samples per pixel into the framebuffer.  Accumulate frames with post_frame(accumulate=True) for a
-        converged reference.  timed=True fills last_times (shade_ms = the launch, rays)."""
+        converged reference.  timed=True fills last_times (shade_ms = the launch, rays).  unbiased=True: the
+        unbiased estimator's direct light instead (render_path(unbiased=True, calc_gi=False))."""
+        if unbiased:
+            return self.render_path(scene, camera, params, frame_index, spp, calc_gi=False, copy_out=copy_out,
+                                    timed=timed, unbiased=True)
         cam = camera_desc(camera)
         out = self.frame_data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if copy_out else None
         self._check(self.lib.rs_render_direct_mis(self.h, scene.h, ctypes.byref(cam), ctypes.byref(params),
@@ -637,17 +642,19 @@ class Renderer:
 
     def render_path(self, scene: Scene, camera, params: FrameParams, frame_index: int = 0, spp: int = 1,
                     max_bounces: int = 5, russian_roulette: bool = True, calc_di: bool = True, calc_gi: bool = True,
-                    copy_out: bool = True, timed: bool = False) -> np.ndarray | None:
+                    copy_out: bool = True, timed: bool = False, unbiased: bool = False) -> np.ndarray | None:
         """NEE path tracer (rs_render_path; NEEPathIntegrator::integrateImpl2 with the MIS direct integrator):
         direct plus indirect light up to max_bounces, spp samples per pixel into the framebuffer.  calc_gi=False
         is render_direct_mis bit for bit.  Accumulate frames with post_frame(accumulate=True).  timed=True fills
-        last_times (shade_ms = the launch, rays)."""
+        last_times (shade_ms = the launch, rays).  unbiased=True: rs_render_path_unbiased, the textbook NEE + MIS
+        estimator over the same material model -- the reference's estimator is dark on materials with kd and ks;
+        params.normal_offset is not used by it."""
         cam = camera_desc(camera)
         pp = PathParams(max_bounces, russian_roulette, calc_di, calc_gi)
         out = self.frame_data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if copy_out else None
-        self._check(self.lib.rs_render_path(self.h, scene.h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(pp),
-                                            int(frame_index), int(spp), out,
-                                            ctypes.byref(self.last_times) if timed else None))
+        fn = self.lib.rs_render_path_unbiased if unbiased else self.lib.rs_render_path
+        self._check(fn(self.h, scene.h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(pp),
+                       int(frame_index), int(spp), out, ctypes.byref(self.last_times) if timed else None))
         return self.frame_data if copy_out else None
 
     def debug_trace(self, scene: Scene, o, d, tnear, tfar, any_hit: bool, lockstep: bool = True,

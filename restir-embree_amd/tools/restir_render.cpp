@@ -6,9 +6,10 @@
 //   restir_render [--obj file.obj] [--w 1920 --h 1080] [--frames 10] [--area 32] [--brdf 1]
 //                 [--spatial k] [--temporal] [--out frame.pfm] [--eye x y z --at x y z --fov deg]
 //                 [--bench] [--ranks N [--compare]] [--denoise weights.tza [--png display.png]]
-//                 [--path SPP [--bounces N]]
+//                 [--path SPP [--bounces N] [--unbiased]]
 // --path SPP: the frames are produceStandard's instead -- the NEE path tracer (direct + indirect light up to N
 // bounces, default 5) at SPP samples per pixel, accumulated like the ReSTIR frames; --out writes the last.
+// --unbiased (only with --path): the unbiased NEE + MIS estimator (rs_render_path_unbiased) instead of the reference's.
 // --bench: the drop-in throughput -- frames/s of produceRestir with frame_data landing in host memory
 // every frame, pipelined (pipelineDepth 2 and 1: readbacks overlapping the next frames, timePasses off)
 // and with the reference's synchronous semantics; one JSON line.
@@ -43,7 +44,7 @@ static void write_pfm(const std::string& path, int W, int H, const float* rgb) {
 int main(int argc, char** argv) {
     std::string obj, out, denoise_w, png;
     int W = 512, H = 512, frames = 5;
-    bool bench = false, cam_set = false, compare = false;
+    bool bench = false, cam_set = false, compare = false, unbiased = false;
     int ranks = 0, path_spp = 0, bounces = 5;
     float eye[3] = {0, 0, 0}, at[3] = {0, 0, 0}, fov = 40.0f;
     restir::Renderer* rp = nullptr;
@@ -67,9 +68,14 @@ int main(int argc, char** argv) {
         else if (a == "--png") png = next();
         else if (a == "--path") path_spp = std::atoi(next());
         else if (a == "--bounces") bounces = std::atoi(next());
+        else if (a == "--unbiased") unbiased = true;
         else if (a == "--eye") { for (float& v : eye) v = (float)std::atof(next()); cam_set = true; }
         else if (a == "--at") { for (float& v : at) v = (float)std::atof(next()); cam_set = true; }
         else if (a == "--fov") fov = (float)std::atof(next());
+    }
+    if (unbiased && path_spp <= 0) {
+        std::fprintf(stderr, "restir_render: --unbiased is valid only with --path SPP\n");
+        return 1;
     }
     // Raytracer::LoadScene: the OBJ file, or the C1 Cornell box built in memory
     auto load = [&](restir::Renderer& r) {
@@ -163,12 +169,14 @@ int main(int argc, char** argv) {
         }
         r.samplesPerPixel = (uint32_t)path_spp;
         r.pathParams.max_bounces = bounces;
+        r.unbiasedEstimator = unbiased;
         for (int f = 0; f < frames; ++f) {
             if (path_spp > 0) {
                 r.produceStandard();
                 r.postFrame();
-                std::printf("frame %d: path tracer %u spp, %d bounces: %.3f ms, rays %llu, accumulator mean %.6f "
-                            "var %.6f (%u frames)\n", f, r.samplesPerPixel, bounces, r.totalFrameDuration,
+                std::printf("frame %d: %spath tracer %u spp, %d bounces: %.3f ms, rays %llu, accumulator mean %.6f "
+                            "var %.6f (%u frames)\n", f, unbiased ? "unbiased " : "", r.samplesPerPixel, bounces,
+                            r.totalFrameDuration,
                             (unsigned long long)r.raysTraced, r.accumulatorMean, r.accumulatorVariance, r.accFrameCtr);
                 continue;
             }

@@ -7,6 +7,13 @@ finished lanes with the next sample buys, since one sample per pixel leaves noth
 next to them, the path oracle's wall time for frame 0 on --threads host threads.
 
   python scripts/path_probe.py [--out profiles/path_probe.json]
+
+--unbiased: the unbiased estimator (rs_render_path_unbiased, csrc/rs_path_unbiased.h) beside the reference's on the
+same four configs instead -- after a warm-up of both, --repeats pairs of launches alternating between the two kernels
+in one session, the median of each.  Writes profiles/path_probe_unbiased.json: ms per launch, rays and Mrays/s of
+both, and unbiased / reference in ms and in rays.
+
+  python scripts/path_probe.py --unbiased [--out profiles/path_probe_unbiased.json]
 """
 import argparse
 import json
@@ -30,6 +37,43 @@ def workload(name):
     return scenes.sponza_like(), P.c3_params()
 
 
+def _row(ms, rays):
+    return {"ms": round(statistics.median(ms), 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4),
+            "rays_frame0": rays, "mrays_per_s": round(rays / (ms[0] * 1e3), 1)}
+
+
+def compare(a):
+    """the reference's estimator and the unbiased one, alternating"""
+    W, H = a.width, a.height
+    res = {"width": W, "height": H, "max_bounces": a.bounces, "repeats": a.repeats,
+           "timer": "rs_pass_times.shade_ms (device events around the launch)",
+           "protocol": "one warm-up launch of each kernel, then reference and unbiased launches alternating", "configs": {}}
+    for name in a.configs.split(","):
+        sc, prm = workload(name)
+        g = Renderer(W, H)
+        gs = g.load_scene(sc)
+        rows = {}
+        for spp in map(int, a.spp.split(",")):
+            ms, rays = {False: [], True: []}, {}
+            for f in range(-1, a.repeats):                      # -1: the warm-up pair
+                for unbiased in (False, True):
+                    g.render_path(gs, sc.camera, prm, max(f, 0), spp, max_bounces=a.bounces, copy_out=False, timed=True,
+                                  unbiased=unbiased)
+                    if f >= 0:
+                        ms[unbiased].append(float(g.last_times.shade_ms))
+                    if f == 0:
+                        rays[unbiased] = int(g.last_times.rays)
+            row = {"reference": _row(ms[False], rays[False]), "unbiased": _row(ms[True], rays[True])}
+            row["ms_unbiased_over_reference"] = round(row["unbiased"]["ms"] / row["reference"]["ms"], 4)
+            row["rays_unbiased_over_reference"] = round(rays[True] / rays[False], 4)
+            rows[f"spp{spp}"] = row
+            print(name, spp, row, flush=True)
+        res["configs"][name] = rows
+        gs.close()                      # a scene goes before its context
+        g.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=1920)
@@ -40,8 +84,12 @@ def main():
     ap.add_argument("--configs", default="C2,C3")
     ap.add_argument("--spp", default="1,8")
     ap.add_argument("--no-oracle", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "path_probe.json"))
+    ap.add_argument("--unbiased", action="store_true")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "path_probe_unbiased.json" if a.unbiased else "path_probe.json")
+    if a.unbiased:
+        return write(a.out, compare(a))
     W, H = a.width, a.height
     res = {"width": W, "height": H, "max_bounces": a.bounces, "repeats": a.repeats, "oracle_threads": a.threads,
            "timer": "rs_pass_times.shade_ms (device events around the launch)", "configs": {}}
@@ -74,8 +122,12 @@ def main():
         res["configs"][name] = rows
         gs.close()                      # a scene goes before its context
         g.close()
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
+    write(a.out, res)
+
+
+def write(out, res):
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
         json.dump(res, f, indent=1)
         f.write("\n")
     print(json.dumps(res))
