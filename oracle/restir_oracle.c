@@ -1674,6 +1674,19 @@ int or_render_frame(or_ctx* c, const or_scene* s, const float* cam7, const or_pa
 #define PASS_MIS 64u
 typedef struct { v3 pos, n, dir, kd, ks, wr; float shin, i_m, maxD, maxS, pf; int phong; } mis_surf;
 
+/* the mis_surf of the hit hi of material record m, reached along d: all maps applied, 1/I_M for Phong */
+static mis_surf mis_surf_at(const or_scene* s, const hitinfo* hi, v3 d, const or_mat* m) {
+    mis_surf h;
+    h.pos = hi->point; h.n = hi->normal; h.dir = d;
+    h.kd = m->kd; h.ks = m->ks; h.shin = m->shin;
+    apply_maps(s, hi->prim, hi->u, hi->v, s->mat[hi->prim], &h.kd, &h.ks, &h.shin, &h.n, 0);
+    h.phong = m->type == MT_PHONG || m->type == MT_DIELECTRIC;
+    h.maxD = maxc(h.kd); h.maxS = maxc(h.ks);
+    h.pf = h.maxD / (h.maxD + h.maxS);
+    h.wr = nrmz(reflect(d, h.n));
+    h.i_m = h.phong ? 1.0f / or_calc_I_M(dot(neg(d), h.n), h.shin) : 0.0f;
+    return h;
+}
 static inline float mis_power(float pdf, float other) {   /* DirectMISIntegrator::powerHeuristic (:10-15) */
     float a = pdf * pdf, b = other * other;
     return a / (b + a);
@@ -1791,19 +1804,10 @@ int or_render_direct_mis(or_ctx* c, const or_scene* s, const float* cam7, const 
                 px = P->use_skybox ? sky_texel(s, d) : V(P->bg_color[0], P->bg_color[1], P->bg_color[2]);
             } else {
                 const or_mat* m = &s->mats[s->mat[hi.prim]];
-                v3 kd = m->kd, ks = m->ks, hn = hi.normal; float shin = m->shin;
-                apply_maps(s, hi.prim, hi.u, hi.v, s->mat[hi.prim], &kd, &ks, &shin, &hn, 0);
                 if (nonzero_pos(m->le)) {                  /* Material::isEmitter, camera vertex */
                     px = m->le;
                 } else {
-                    mis_surf h;
-                    h.pos = hi.point; h.n = hn; h.dir = d;
-                    h.kd = kd; h.ks = ks; h.shin = shin;
-                    h.phong = m->type == MT_PHONG || m->type == MT_DIELECTRIC;
-                    h.maxD = maxc(h.kd); h.maxS = maxc(h.ks);
-                    h.pf = h.maxD / (h.maxD + h.maxS);
-                    h.wr = nrmz(reflect(d, h.n));
-                    h.i_m = h.phong ? 1.0f / or_calc_I_M(dot(neg(d), h.n), h.shin) : 0.0f;
+                    const mis_surf h = mis_surf_at(s, &hi, d, m);
                     rng_t rng = rng_init(P->seed, frame_index, PASS_MIS, (uint32_t)p);
                     v3 acc = V(0, 0, 0);
                     for (int k = 0; k < spp; ++k) {

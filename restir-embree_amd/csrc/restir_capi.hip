@@ -7,7 +7,6 @@
 #include "rs_passes.h"
 #include "rs_mis.h"
 #include "rs_path.h"
-#include "rs_path_unbiased.h"
 #include "rs_post.h"
 #include "rs_refit.h"
 #include "../../include/restir_c.h"
@@ -2073,15 +2072,15 @@ extern "C" int rs_render_path(rs_context* c, const rs_scene* s, const rs_camera*
                               const rs_path_params* pp, uint32_t frame_index, uint32_t spp, float* frame_rgb_host,
                               rs_pass_times* t) {
     return render_path_with(c, s, cam, P, pp, frame_index, spp, frame_rgb_host, t, "rs_render_path",
-                            [](auto T) { return &k_path_nee<T()>; });
+                            [](auto T) { return &k_path<T(), kEstReference>; });
 }
 
-// The unbiased NEE + MIS path tracer (rs_path_unbiased.h)
+// The unbiased NEE + MIS path tracer (rs_path.h, kEstUnbiased)
 extern "C" int rs_render_path_unbiased(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
                                        const rs_path_params* pp, uint32_t frame_index, uint32_t spp,
                                        float* frame_rgb_host, rs_pass_times* t) {
     return render_path_with(c, s, cam, P, pp, frame_index, spp, frame_rgb_host, t, "rs_render_path_unbiased",
-                            [](auto T) { return &k_path_unbiased<T()>; });
+                            [](auto T) { return &k_path<T(), kEstUnbiased>; });
 }
 
 extern "C" int rs_get_frame_device_ptr(rs_context* c, const float** dptr) {

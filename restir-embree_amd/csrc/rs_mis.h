@@ -18,6 +18,9 @@
 namespace rs {
 
 constexpr uint32_t kPassMis = 64u;
+// the estimators of the ground truths: the reference's, restated bit for bit with its three biases, and
+// the textbook NEE + MIS one over the same material model (rs_path.h)
+constexpr int kEstReference = 0, kEstUnbiased = 1;
 
 struct MisSurf { vec3 pos, n, wr, kd, ks; float shin, i_m, maxD, maxS, pf; bool phong; };
 
@@ -57,27 +60,54 @@ __device__ __forceinline__ vec3 mis_brdf(const MisSurf& h, const LobePow& lp) {
     if (!h.phong) return f;
     return f + (h.ks * h.i_m) * lp.brdf;
 }
-// evaluateLightingGI (pg/MaterialLambert.cpp:10-18, pg/MaterialPhong.cpp:18-67)
+// evaluateLightingGI (pg/MaterialLambert.cpp:10-18, pg/MaterialPhong.cpp:18-67): the lobe choice, wi, one power for
+// the pdf and the BRDF, the mixture pdf, f_r zeroed below the surface.  f_r is the estimator's own.  The reference's is
+// the sampled lobe's, and its Lambert returns early with kd / pi, never zeroed; the unbiased one's is the full BRDF on
+// wi (kd * (1 / pi) + ...: other bits).  Past the Lambert return the reference's form has h.phong true; the conditions
+// spell that out (E == kEstReference ||) so that its kernels compile to the text they had before the two forms met.
+template <int E>
 __device__ __forceinline__ vec3 mis_sample(const MisSurf& h, Rng& rng, vec3& f_r, float& pdf) {
-    if (!h.phong) {
+    if (E == kEstReference && !h.phong) {
         vec3 wi = cosine_sample(h.n, rng);
         pdf = cos_pdf(h.n, wi);
         f_r = dvs(h.kd, kPi);
         return wi;
     }
-    float r0 = rng.range(0.0f, h.maxD + h.maxS);
+    bool diffuse = true;
+    if (E == kEstReference || h.phong) diffuse = rng.range(0.0f, h.maxD + h.maxS) < h.maxD;
     vec3 wi;
-    const bool diffuse = r0 < h.maxD;
     if (diffuse) wi = cosine_sample(h.n, rng);
     else wi = lobe_sample(h.wr, h.shin, rng);
     const LobePow lp = mis_lobe_pow(h, wi);
-    if (diffuse) f_r = h.kd * kOneOverPi;
-    else f_r = (h.ks * h.i_m) * lp.brdf;
-    float pd = cos_pdf(h.n, wi) * h.pf;
-    float ps = lobe_pdf(h.shin, lp.pdf) * (1.0f - h.pf);
-    pdf = pd + ps;
+    if constexpr (E == kEstUnbiased) {
+        pdf = mis_pdf_for(h, wi, lp);
+        f_r = mis_brdf(h, lp);
+    } else {
+        if (diffuse) f_r = h.kd * kOneOverPi;
+        else f_r = (h.ks * h.i_m) * lp.brdf;
+        float pd = cos_pdf(h.n, wi) * h.pf;
+        float ps = lobe_pdf(h.shin, lp.pdf) * (1.0f - h.pf);
+        pdf = pd + ps;
+    }
     if (dot(h.n, wi) < 0) f_r = mk(0, 0, 0);
     return wi;
+}
+
+// The BRDF ray from `from`, drawn with solid-angle pdf `pdf`, hit the emitter b of material record m: the power
+// heuristic's weight of that strategy (pg/DirectMISIntegrator.cpp:118-140); kCosI: cI becomes the cosine at `from`, normal n,
+// in the place the operation had in mis_brdf_part; the unbiased vertex does not want it and its cI stays untouched
+template <bool kCosI>
+__device__ __forceinline__ float mis_emitter_w(const DevScene& S, vec3 from, vec3 n, float pdf, const SurfHit& b, MatRec m,
+                                               float& cI) {
+    vec3 bn = b.normal;
+    if (S.texd) apply_maps(S, b, m, bn, true);
+    vec3 ld = b.point - from;
+    float r2 = dot(ld, ld);
+    ld = normalize(ld);
+    if constexpr (kCosI) cI = gmax(dot(ld, n), 0.0f);
+    float cY = gmax(dot(-ld, bn), 0.0f);
+    float amf = cY / r2;
+    return mis_power(pdf * amf, emis_pdf_brdf(S, b.emis_id));     // TriangleCDF::getPDFForTriangle
 }
 
 // DirectMISIntegrator::evaluateBRDFSample (pg/DirectMISIntegrator.cpp:94-144).  BRDF rays are
@@ -87,22 +117,14 @@ __device__ __forceinline__ vec3 mis_brdf_part(const DevScene& S, const FrameCons
                                               Rng& rng, uint32_t& rays) {
     vec3 f_r;
     float pdf;
-    vec3 wi = mis_sample(h, rng, f_r, pdf);
+    vec3 wi = mis_sample<kEstReference>(h, rng, f_r, pdf);
     rays += alive ? 1u : 0u;
     SurfHit b = intersect<T | TRAV_LANE>(S, alive, h.pos + h.n * F.normal_off, wi, FLT_MIN + F.tnear_off);
     if (!b.hit) return mk(0, 0, 0);
     MatRec m = load_mat(S, b.mat);
     if (!(m.le.x + m.le.y + m.le.z > 0)) return mk(0, 0, 0);      // Material::isEmissive
-    vec3 bn = b.normal;
-    if (S.texd) apply_maps(S, b, m, bn, true);
-    vec3 ld = b.point - h.pos;
-    float r2 = dot(ld, ld);
-    ld = normalize(ld);
-    float cI = gmax(dot(ld, h.n), 0.0f);
-    float cY = gmax(dot(-ld, bn), 0.0f);
-    float amf = cY / r2;
-    float pdf_light = emis_pdf_brdf(S, b.emis_id);                 // TriangleCDF::getPDFForTriangle
-    float w = mis_power(pdf * amf, pdf_light);
+    float cI;
+    float w = mis_emitter_w<true>(S, h.pos, h.n, pdf, b, m, cI);
     return dvs(((m.le * w) * f_r) * cI, pdf);
 }
 

@@ -1,4 +1,5 @@
-// rs_path.h -- NEE path tracer: the global-illumination ground truth.
+// rs_path.h -- the NEE path tracers: the global-illumination ground truths, one kernel for
+// the two estimators.  The reference's:
 //
 // SimpleGuiDX11::produceStandard (pg/simpleguidx11.cpp:336-357) driving NEEPathIntegrator::integrateImpl2
 // (pg/NEEPathIntegrator.cpp:72-131) with calcGI on: at every path vertex the MIS direct estimate of rs_mis.h
@@ -7,12 +8,13 @@
 // bounce > 5; an emitter counts only at the camera vertex (next-event estimation).  Material model of rs_mis.h
 // (MisSurf: Phong for PHONG/DIELECTRIC, Lambert otherwise), so this image, the MIS image and the ReSTIR image
 // estimate the same scene.  RNG: pass kPassMis, one stream per pixel, draws in the recursion's order over the
-// samples -- with calc_gi off the draws, and the frame, are k_direct_mis's.  Restated as the recursion in
-// tests/cpp/path_oracle.c or_render_path.
+// samples -- with calc_gi off the draws, and the frame, are k_direct_mis's.  Restated as the recursion path_L in
+// tests/cpp/path_oracle.c (or_render_path); the unbiased estimator is defined by upath_L there (or_render_path_unbiased).
+// The kernel equals both bit for bit.
 //
 // The recursion is unrolled into one wave-uniform loop.  sanitize() between the levels is not linear, so a
 // forward throughput product would give other floats: every vertex of the path in flight leaves an 8-float
-// record (Ld, f_r, |cos|, pdf * RR) and the finished path is folded deepest level first, exactly as the return
+// record (Ld, f_r, |cos|, pdf * q) and the finished path is folded deepest level first, exactly as the return
 // statements would.  The records live in dynamic LDS, level-major: field f of level l of thread t at
 // rec[(l * 8 + f) * 256 + t] -- consecutive lanes on consecutive banks, every thread in its own column, so the
 // loop needs no barrier; (max_bounces + 1) * 8 KiB per workgroup.
@@ -48,8 +50,21 @@ __device__ __forceinline__ MisSurf path_surf(const DevScene& S, const SurfHit& h
     return h;
 }
 
-template <int T>
-__global__ void __launch_bounds__(kPathBlock) k_path_nee(DevScene S, FrameConst F, PathConst Q, float* fb, CountSlot C) {
+template <int T, int E>
+__global__ void __launch_bounds__(kPathBlock) k_path(DevScene S, FrameConst F, PathConst Q, float* fb, CountSlot C) {
+    // E = kEstReference restates the reference's estimator bit for bit, three biases included.
+    // E = kEstUnbiased is the textbook estimator over the same material model, free of the reference's structure: per
+    // vertex one light sample with its shadow ray (mis_light_part, unchanged) and one BRDF sample whose ray does both
+    // jobs -- an emitter it finds is the BRDF strategy's direct estimate (Le * power weight, resolved where the ray was
+    // traced), any other surface is the next vertex.  What differs from the reference's:
+    //   - the BRDF sample carries the full BRDF (mis_brdf) over the mixture pdf, not the sampled lobe's;
+    //   - its ray starts at the surface point h.pos, where the shadow rays start, so both MIS strategies measure a
+    //     light point from one origin and their weights sum to one.  FrameConst::normal_off (rs_frame_params::
+    //     normal_offset) is NOT used by this estimator; self-hits are kept off by tnear = FLT_MIN + tnear_offset;
+    //   - Russian roulette (bounce > 5, q = min(max(maxc Kd, maxc Ks) of the record, 1)) is drawn after the emitter
+    //     test and divides the whole return of the vertex, direct part included: its record is (Ld / q, ...);
+    //   - one closest-hit ray per vertex instead of two: two walks per iteration, not three.
+    constexpr bool U = E == kEstUnbiased;
     extern __shared__ __attribute__((aligned(16))) float path_rec[];
     constexpr int TL = T | TRAV_LANE;               // past the camera vertex every ray is incoherent
     float* const rec = path_rec + threadIdx.x;
@@ -70,8 +85,8 @@ __global__ void __launch_bounds__(kPathBlock) k_path_nee(DevScene S, FrameConst 
     Rng rng; rng.init(F.seed, F.frame, kPassMis, pix);
     vec3 acc = mk(0, 0, 0);
     MisSurf h = h0;                                                  // the vertex this iteration handles
-    int k = surf ? 0 : Q.spp, b = 0;                                 // sample and bounce of that vertex
-    float rrs = 1.0f;                                                // its (bounce > 5 && RR) ? maxThroughput : 1
+    int k = surf ? 0 : Q.spp, b = 0;                               // sample and bounce of that vertex
+    float q = 1.0f;                                                  // its (bounce > 5 && RR) ? survival probability : 1
     // every iteration moves every live lane one vertex on and a sample has at most max_bounces + 1 of them, so
     // the bound is never what ends the loop; it is there so that nothing can spin
     const uint32_t cap = (uint32_t)Q.spp * (uint32_t)(Q.max_bounces + 1);
@@ -80,42 +95,74 @@ __global__ void __launch_bounds__(kPathBlock) k_path_nee(DevScene S, FrameConst 
         if (__ballot(live) == 0) break;
         vec3 Ld = mk(0, 0, 0);
         if (Q.di) {
-            Ld = mk(0, 0, 0) + mis_brdf_part<TL>(S, F, h, live, rng, rays);
-            Ld = Ld + mis_light_part<TL>(S, F, h, live, rng, rays);
+            if constexpr (!U) {
+                Ld = mk(0, 0, 0) + mis_brdf_part<TL>(S, F, h, live, rng, rays);
+                Ld = Ld + mis_light_part<TL>(S, F, h, live, rng, rays);
+            } else {
+                Ld = mk(0, 0, 0) + mis_light_part<TL>(S, F, h, live, rng, rays);
+            }
         }
         Ld = sanitize(Ld);
+        if constexpr (U) Ld = dvs(Ld, q);
         vec3 R = mk(0, 0, 0);                                        // what the continuation ray brings back
         bool more = false;                                           // the path goes on at the next hit
         MisSurf hx = h;
-        if (Q.gi) {
+        float qx = 1.0f;                                             // unbiased: the next vertex's q
+        if (U || Q.gi) {                                             // the reference draws nothing with GI off
             vec3 f_r;
             float pdf;
-            const vec3 wi = mis_sample(h, rng, f_r, pdf);            // drawn even when the limit ends the path here
-            const bool go = live && !(b + 1 > Q.max_bounces);        // (:75-76) no ray beyond the limit
+            const vec3 wi = mis_sample<E>(h, rng, f_r, pdf);         // drawn even when the limit ends the path here
+            bool last, go;                                           // this is the last vertex; its ray is traced
+            if constexpr (!U) {
+                last = b + 1 > Q.max_bounces;
+                go = live && !last;                                  // (:75-76) no ray beyond the limit
+            } else {
+                last = !Q.gi || b + 1 > Q.max_bounces;               // the next hit counts as an emitter only,
+                go = live && !(last && !Q.di);                       // which nobody asks for with the direct part off
+            }
             rays += go ? 1u : 0u;
-            const SurfHit nx = intersect<TL>(S, go, h.pos + h.n * F.normal_off, wi, FLT_MIN + F.tnear_off);
+            const vec3 org = U ? h.pos : h.pos + h.n * F.normal_off; // unbiased: from where the shadow rays start
+            const SurfHit nx = intersect<TL>(S, go, org, wi, FLT_MIN + F.tnear_off);
             if (live) {
                 float* r = rec + b * (kPathRec * kPathBlock);
                 r[0 * kPathBlock] = Ld.x; r[1 * kPathBlock] = Ld.y; r[2 * kPathBlock] = Ld.z;
                 r[3 * kPathBlock] = f_r.x; r[4 * kPathBlock] = f_r.y; r[5 * kPathBlock] = f_r.z;
                 r[6 * kPathBlock] = fabsf(dot(wi, h.n));
-                r[7 * kPathBlock] = pdf * rrs;
+                r[7 * kPathBlock] = pdf * q;
             }
             const MatRec mx = load_mat(S, nx.mat);
-            if (go && !nx.hit) R = F.use_sky ? sky_texel(S, wi) : F.bg;
+            if (go && !nx.hit && (!U || !last)) R = F.use_sky ? sky_texel(S, wi) : F.bg;
             if (go && nx.hit) {
                 const float maxT = gmax(maxc(mx.kd), maxc(mx.ks));   // the record's colours, not the mapped ones
                 const bool rr = b + 1 > 5 && Q.rr;
+                // The reference's arm makes q the next vertex's factor in place (a second variable carried over
+                // path_surf's call costs its kernels a VGPR).  That is sound only in this order: this vertex's record,
+                // pdf * q, is final above, and more implies live.  The unbiased arm, whose q also divides Ld, carries
+                // qx to the step below.
                 bool cut = false;
-                if (rr) cut = maxT <= rng.range(0.0f, 1.0f);          // the draw is made only under roulette
-                more = !cut && !any_pos(mx.le);                      // an emitter past the camera vertex: 0 (NEE)
-                if (more) rrs = rr ? maxT : 1.0f;
+                if constexpr (!U) {                                  // roulette first; the draw is made only under it
+                    if (rr) cut = maxT <= rng.range(0.0f, 1.0f);
+                    more = !cut && !any_pos(mx.le);                  // an emitter past the camera vertex: 0 (NEE)
+                    if (more) q = rr ? maxT : 1.0f;
+                } else if (any_pos(mx.le)) {                         // the BRDF strategy's direct estimate
+                    float cI;
+                    if (Q.di) R = mx.le * mis_emitter_w<false>(S, h.pos, h.n, pdf, nx, mx, cI);
+                } else if (!last) {
+                    if (rr) {
+                        qx = gmin(maxT, 1.0f);
+                        cut = qx <= rng.range(0.0f, 1.0f);
+                    }
+                    more = !cut;
+                }
             }
             hx = path_surf(S, nx, mx, wi, more);
         }
-        if (live && more) { h = hx; ++b; }
+        if (live && more) {
+            h = hx; ++b;
+            if constexpr (U) q = qx;
+        }
         if (live && !more) {
-            if (Q.gi) {
+            if (U || Q.gi) {
                 for (int l = b; l >= 0; --l) {
                     const float* r = rec + l * (kPathRec * kPathBlock);
                     const vec3 ld = mk(r[0 * kPathBlock], r[1 * kPathBlock], r[2 * kPathBlock]);
@@ -124,10 +171,10 @@ __global__ void __launch_bounds__(kPathBlock) k_path_nee(DevScene S, FrameConst 
                     R = li + ld;                                                                      // (:129)
                 }
             } else {
-                R = mk(0, 0, 0) + Ld;
+                R = mk(0, 0, 0) + Ld;                                // the 0 + matters for -0
             }
             acc = acc + R;
-            ++k; b = 0; h = h0; rrs = 1.0f;
+            ++k; b = 0; h = h0; q = 1.0f;
         }
     }
     if (surf) px = dvs(acc, (float)Q.spp);

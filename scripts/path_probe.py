@@ -8,7 +8,7 @@ next to them, the path oracle's wall time for frame 0 on --threads host threads.
 
   python scripts/path_probe.py [--out profiles/path_probe.json]
 
---unbiased: the unbiased estimator (rs_render_path_unbiased, csrc/rs_path_unbiased.h) beside the reference's on the
+--unbiased: the unbiased estimator (rs_render_path_unbiased, k_path<T, kEstUnbiased>) beside the reference's on the
 same four configs instead -- after a warm-up of both, --repeats pairs of launches alternating between the two kernels
 in one session, the median of each.  Writes profiles/path_probe_unbiased.json: ms per launch, rays and Mrays/s of
 both, and unbiased / reference in ms and in rays.

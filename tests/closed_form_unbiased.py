@@ -1,5 +1,5 @@
 """Closed-form references and recorded bounds of the unbiased path tracer (rs_render_path_unbiased; checker
-tests/cpp/path_unbiased_oracle.c).  TEST INFRASTRUCTURE ONLY.
+tests/cpp/path_oracle.c).  TEST INFRASTRUCTURE ONLY.
 
 Scenes, references, measure(), the seeds and the caps are closed_form's.  This module adds what the new estimator
 needs of its own: its estimator table, the quad under a uniform background (a closed form that exercises the
@@ -72,7 +72,7 @@ def frame_params(scene, seed):
 
 # ---------------------------------------------------------------- the recorded checker figures and the bounds from them
 # "scene/estimator/region": (ratio: mean over SEEDS, sd: over MEASURE_SEEDS, per-pixel median, p99) -- the checker's
-# (tests/cpp/path_unbiased_oracle.c) figures at samples_for(scene) samples per pixel
+# (tests/cpp/path_oracle.c) figures at samples_for(scene) samples per pixel
 MEASURED = {
     "open/unbiased/all": (1.0005, 0.00117, 0.0083, 0.0397),
     "blocked/unbiased/lit": (1.0019, 0.00211, 0.0084, 0.0394),

@@ -1,5 +1,5 @@
-"""ctypes wrapper for the path-tracer checker (tests/cpp/path_oracle.c: or_render_path over the oracle's own
-statics).  TEST INFRASTRUCTURE ONLY.
+"""ctypes wrapper for the path-tracer checkers (tests/cpp/path_oracle.c: or_render_path and or_render_path_unbiased
+over the oracle's own statics).  TEST INFRASTRUCTURE ONLY.
 
 The file includes oracle/restir_oracle.c and is compiled on demand with exactly the flags of oracle/Makefile, so
 scene and context handles made by oracle_lib (same source, same flags, same layouts) may be passed to it.  Also
@@ -32,25 +32,28 @@ def lib():
         if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(p) for p in DEPS):
             subprocess.check_call([os.environ.get("CC", "gcc"), *CFLAGS, "-shared", "-o", SO, SRC, "-lm"])
         L = ctypes.CDLL(SO)
-        L.or_render_path.restype = ctypes.c_int
-        L.or_render_path.argtypes = [ctypes.c_void_p, ctypes.c_void_p, O._f32p, ctypes.POINTER(FrameParams),
-                                     ctypes.POINTER(PathParams), ctypes.c_uint32, ctypes.c_int, O._f32p,
-                                     ctypes.POINTER(ctypes.c_uint64)]
+        for fn in (L.or_render_path, L.or_render_path_unbiased):
+            fn.restype = ctypes.c_int
+            fn.argtypes = [ctypes.c_void_p, ctypes.c_void_p, O._f32p, ctypes.POINTER(FrameParams),
+                           ctypes.POINTER(PathParams), ctypes.c_uint32, ctypes.c_int, O._f32p,
+                           ctypes.POINTER(ctypes.c_uint64)]
         _lib = L
     return _lib
 
 
 def render_path(orenderer, oscene, camera, params, frame_index=0, spp=1, max_bounces=5, russian_roulette=True,
-                calc_di=True, calc_gi=True):
-    """or_render_path on an oracle_lib.OracleRenderer / OracleScene pair: one (H, W, 3) frame; .rays on the renderer."""
+                calc_di=True, calc_gi=True, unbiased=False):
+    """or_render_path, or or_render_path_unbiased, on an oracle_lib.OracleRenderer / OracleScene pair: one (H, W, 3)
+    frame; .rays on the renderer."""
     cam = np.ascontiguousarray(camera.as_array() if hasattr(camera, "as_array") else camera, np.float32)
     out = np.zeros((orenderer.H, orenderer.W, 3), np.float32)
     rays = ctypes.c_uint64()
     pp = PathParams(max_bounces, russian_roulette, calc_di, calc_gi)
-    rc = lib().or_render_path(orenderer.h, oscene.h, O._ptr(cam), ctypes.byref(params), ctypes.byref(pp), frame_index,
+    name = "or_render_path_unbiased" if unbiased else "or_render_path"
+    rc = getattr(lib(), name)(orenderer.h, oscene.h, O._ptr(cam), ctypes.byref(params), ctypes.byref(pp), frame_index,
                               spp, O._ptr(out), ctypes.byref(rays))
     if rc != 0:
-        raise RuntimeError(f"or_render_path failed: {rc}")
+        raise RuntimeError(f"{name} failed: {rc}")
     orenderer.rays = int(rays.value)
     return out
 

@@ -1,5 +1,5 @@
-"""GPU tests of the unbiased path tracer (rs_render_path_unbiased, restir-embree_amd/csrc/rs_path_unbiased.h): bit for
-bit against its checker (tests/cpp/path_unbiased_oracle.c, pinned to the light by tests/test_path_unbiased_oracle.py)
+"""GPU tests of the unbiased path tracer (rs_render_path_unbiased, restir-embree_amd/csrc/rs_path.h): bit for bit
+against its checker (tests/cpp/path_oracle.c or_render_path_unbiased, pinned to the light by tests/test_path_unbiased_oracle.py)
 on the same seeds, ray count included; against the closed forms directly, never reading the checker; ReSTIR against
 this new truth on the Phong furnace; and the contract of rs_render_path -- errors, untouched ReSTIR history, the C++
 tool's --path --unbiased frames."""
@@ -14,7 +14,6 @@ import closed_form as CF
 import closed_form_unbiased as CU
 import oracle_lib as O
 import path_oracle as PO
-import path_unbiased_oracle as PU
 from restir_amd import params as P
 from restir_amd import scenes
 from restir_amd.renderer import Renderer, RestirError, camera_desc, decode_image
@@ -69,7 +68,7 @@ def test_unbiased_path_equals_checker(which):
     for i, kw in enumerate(runs):
         for f in range(2):
             assert np.array_equal(out["lockstep", i, f], out["lane", i, f])
-            ref = PU.render_path(o, os_, sc.camera, prm, f, spp, max_bounces=mb, **kw)
+            ref = PO.render_path(o, os_, sc.camera, prm, f, spp, max_bounces=mb, unbiased=True, **kw)
             n_diff = int((out["lane", i, f] != ref).any(axis=-1).sum())
             print(f"[unbiased] {which} {kw} frame {f}: {n_diff} of {W * H} pixels not bit-identical, rays "
                   f"{rays['lane', i, f]} (checker {o.rays})")
@@ -92,7 +91,7 @@ def test_sky_and_maps_match_checker():
     gs = g.load_scene(sc)
     for f in range(2):
         gpu = g.render_path(gs, sc.camera, prm, f, 2, max_bounces=3, unbiased=True).copy()
-        ref = PU.render_path(o, os_, sc.camera, prm, f, 2, max_bounces=3)
+        ref = PO.render_path(o, os_, sc.camera, prm, f, 2, max_bounces=3, unbiased=True)
         assert np.isfinite(gpu).all()
         diff = np.linalg.norm(gpu.astype(np.float64) - ref, axis=-1)
         rel = diff / np.maximum(np.linalg.norm(ref.astype(np.float64), axis=-1), 1e-3)

@@ -3,7 +3,7 @@ with and without TRAV_WIDE; the rest of the suite renders only scenes whose 8-wi
 Kind<TRAV_LOCKSTEP> -- what runs under RESTIR_WIDE=off and, automatically, for a scene with a non-finite vertex or a
 tree deeper than the walk's stack -- never rendered a frame under test.  Here they do: closest_lane_from /
 occluded_lane_from inside the ReSTIR passes, the lockstep kernels' per-lane BRDF rays on the skip pointers, the
-`else` arms of the sorted initial / temporal / spatial passes for T = TRAV_LANE, k_path_nee and the MIS ground truth
+`else` arms of the sorted initial / temporal / spatial passes for T = TRAV_LANE, k_path and the MIS ground truth
 without a wide tree, and k_scene_update with no wide refit to do.
 
 The reference of every case is the same run with the wide tree live: frames, reservoirs, G-buffer and the ray count
@@ -167,7 +167,7 @@ def test_spatial_mis_two_passes(scns, mis, walk, monkeypatch):
 
 @pytest.mark.parametrize("walk", WALKS)
 def test_ground_truths(scns, walk, monkeypatch):
-    """render_direct_mis (spp 2) and render_path (spp 2, 3 bounces): k_path_nee and the MIS integrator on the skip
+    """render_direct_mis (spp 2) and render_path (spp 2, 3 bounces): k_path and the MIS integrator on the skip
     pointers equal the wide-tree launches bit for bit, rays included"""
     sc, (W, H) = scns["c3"], SIZE["c3"]
     prm = P.c3_params()

@@ -1,4 +1,4 @@
-"""CPU tests: the checker of the unbiased path tracer (tests/cpp/path_unbiased_oracle.c or_render_path_unbiased, which
+"""CPU tests: the checker of the unbiased path tracer (tests/cpp/path_oracle.c or_render_path_unbiased, which
 tests/test_gpu_path_unbiased.py holds rs_render_path_unbiased against bit for bit) against lighting known in closed
 form: the Phong furnaces and the occluder scenes of tests/closed_form.py with no quirk rows, a quad under a uniform
 background (the continuation sample), and the integrating sphere at every bounce limit, roulette included.  Bounds:
@@ -10,7 +10,6 @@ import closed_form as CF
 import closed_form_unbiased as CU
 import oracle_lib as O
 import path_oracle as PO
-import path_unbiased_oracle as PU
 from restir_amd import params as P
 from restir_amd import scenes
 
@@ -34,7 +33,7 @@ class OracleBackend:
 
     def mean_image(self, cf, estimator, seed, n):
         o, os_ = self._pair(cf)
-        return PU.render_path(o, os_, cf.camera, CU.frame_params(cf.name, seed), 0, n,
+        return PO.render_path(o, os_, cf.camera, CU.frame_params(cf.name, seed), 0, n, unbiased=True,
                               **CU.ESTIMATORS[estimator]).astype(np.float64)
 
 
@@ -90,12 +89,13 @@ def sphere():
 _sphere_got = {}
 
 
-def _sphere(sphere, m, render=PU.render_path):
+def _sphere(sphere, m, unbiased=True):
     sc, f, o, os_ = sphere
-    if (render, m) not in _sphere_got:
+    if (unbiased, m) not in _sphere_got:
         prm = P.default_params(use_skybox=0)
-        _sphere_got[render, m] = PO.sphere_measure(lambda fr: render(o, os_, sc.camera, prm, fr, 64, max_bounces=m))
-    return _sphere_got[render, m]
+        _sphere_got[unbiased, m] = PO.sphere_measure(
+            lambda fr: PO.render_path(o, os_, sc.camera, prm, fr, 64, max_bounces=m, unbiased=unbiased))
+    return _sphere_got[unbiased, m]
 
 
 @pytest.mark.parametrize("m", [0, 1, 3, 6, 12])
@@ -109,7 +109,7 @@ def test_integrating_sphere_closed_form(sphere, m):
 
 def test_roulette_no_longer_darkens_the_sphere(sphere):
     """m = 12: the reference's estimator divides only the indirect part by the survival probability, so it is lower."""
-    ref, got = _sphere(sphere, 12, PO.render_path), _sphere(sphere, 12)
+    ref, got = _sphere(sphere, 12, unbiased=False), _sphere(sphere, 12)
     print(f"m=12: the reference's estimator {ref:.6f}, unbiased {got:.6f}")
     assert ref < got
 
@@ -121,15 +121,15 @@ def test_plumbing():
     fn, W, H, spp, mb = PARITY_SMALLEST
     sc, prm = fn(), P.default_params()
     o, os_ = O.OracleRenderer(W, H), O.OracleScene(sc)
-    a = PU.render_path(o, os_, sc.camera, prm, 0, spp, max_bounces=mb)
+    a = PO.render_path(o, os_, sc.camera, prm, 0, spp, max_bounces=mb, unbiased=True)
     rays = o.rays
-    assert np.array_equal(a, PU.render_path(o, os_, sc.camera, prm, 0, spp, max_bounces=mb)) and o.rays == rays
-    assert not np.array_equal(a, PU.render_path(o, os_, sc.camera, prm, 1, spp, max_bounces=mb))
+    assert np.array_equal(a, PO.render_path(o, os_, sc.camera, prm, 0, spp, max_bounces=mb, unbiased=True)) and o.rays == rays
+    assert not np.array_equal(a, PO.render_path(o, os_, sc.camera, prm, 1, spp, max_bounces=mb, unbiased=True))
     PO.render_path(o, os_, sc.camera, prm, 0, spp, max_bounces=mb)
     print(f"rays: unbiased {rays}, the reference's estimator {o.rays} ({rays / o.rays:.3f})")
     assert W * H < rays < o.rays
     # neither strategy: black on surfaces, emitters and the background as seen, primary rays only
-    black = PU.render_path(o, os_, sc.camera, prm, 0, spp, max_bounces=mb, calc_di=False, calc_gi=False)
+    black = PO.render_path(o, os_, sc.camera, prm, 0, spp, max_bounces=mb, calc_di=False, calc_gi=False, unbiased=True)
     assert o.rays == W * H
     o.render(os_, sc.camera, prm, 0)
     g = o.gbuffer()
