@@ -254,18 +254,21 @@ public:
     // one frame as N bands, gathered into frame_data() (synchronous)
     void produceRestir(float t = 0.0f) {
         (void)t;
-        if (!m_) {
-            std::vector<rs_context*> ctxs;
-            for (auto* r : ranks_) ctxs.push_back(r->handle());
-            check(rs_mgpu_create_local(ctxs.data(), (int)ctxs.size(), &m_), ranks_[0]->handle());
-        }
-        std::vector<const rs_scene*> scenes;
-        for (auto* r : ranks_) {
-            if (!r->scene_handle()) throw Error(RS_E_INVALID, "MultiGpuRenderer: load the scene into every rank");
-            scenes.push_back(r->scene_handle());
-        }
+        const std::vector<const rs_scene*> scenes = group();
         check(rs_mgpu_render_frame(m_, scenes.data(), &camera_, &params, frameCtr, 1, frame_.data(), nullptr),
               ranks_[0]->handle());
+        ++frameCtr;
+    }
+    // Renderer::produceStandard on all ranks (rs_mgpu_render_ground_truth): samplesPerPixel paths per pixel under
+    // pathParams, rank r rendering the 16-row strips r, r + N, ...; gathered into frame_data() (synchronous),
+    // bit-identical to one Renderer's frame.  The ReSTIR history and the bands are untouched; rank(0).postFrame()
+    // then accumulates the full frame.
+    void produceStandard(float t = 0.0f) {
+        (void)t;
+        const std::vector<const rs_scene*> scenes = group();
+        check(rs_mgpu_render_ground_truth(m_, scenes.data(), &camera_, &params,
+                                          unbiasedEstimator ? RS_GT_PATH_UNBIASED : RS_GT_PATH, &pathParams, frameCtr,
+                                          samplesPerPixel, 1, frame_.data(), nullptr), ranks_[0]->handle());
         ++frameCtr;
     }
     // cost-balanced bands from n_frames of per-row wave times, then `refine` rounds of time-based refinement
@@ -282,9 +285,27 @@ public:
 
     Camera camera_;
     Params params;
+    // produceStandard (as Renderer's members)
+    rs_path_params pathParams{5, 1, 1, 1};
+    uint32_t samplesPerPixel = 1;
+    bool unbiasedEstimator{false};
     uint32_t frameCtr = 0;
 
 private:
+    // the rank group, created on first use, and every rank's scene
+    std::vector<const rs_scene*> group() {
+        if (!m_) {
+            std::vector<rs_context*> ctxs;
+            for (auto* r : ranks_) ctxs.push_back(r->handle());
+            check(rs_mgpu_create_local(ctxs.data(), (int)ctxs.size(), &m_), ranks_[0]->handle());
+        }
+        std::vector<const rs_scene*> scenes;
+        for (auto* r : ranks_) {
+            if (!r->scene_handle()) throw Error(RS_E_INVALID, "MultiGpuRenderer: load the scene into every rank");
+            scenes.push_back(r->scene_handle());
+        }
+        return scenes;
+    }
     int width_, height_;
     std::vector<Renderer*> ranks_;
     rs_mgpu* m_ = nullptr;

@@ -249,6 +249,29 @@ int rs_render_path(rs_context* ctx, const rs_scene* scene, const rs_camera* came
 int rs_render_path_unbiased(rs_context* ctx, const rs_scene* scene, const rs_camera* camera,
                             const rs_frame_params* params, const rs_path_params* path, uint32_t frame_index,
                             uint32_t spp, float* frame_rgb_host, rs_pass_times* times);
+/* ---- A ground truth over a row set: the single-context piece of a multi-GPU ground truth ------------- */
+/* The rows y in [0, H) with (y / strip_rows) % stride == phase: strips of strip_rows rows (a positive multiple
+ * of RS_ROW_STRIP, the height of a workgroup's pixel tile) dealt out round robin to `stride` owners, this one
+ * being owner `phase`.  A ground-truth pixel is independent of every other and its random stream is keyed by
+ * the full-frame pixel index, so the strips of all phases assemble the full-frame entry's frame bit for bit;
+ * {RS_ROW_STRIP, 1, 0} is that entry.  estimator picks rs_render_direct_mis (path = NULL), rs_render_path or
+ * rs_render_path_unbiased, whose contract, error codes and ranges hold: one launch on the context's stream,
+ * ReSTIR history untouched.  Only the rows of the set are written, every other row of the framebuffer keeps its
+ * contents (frame_rgb_host receives the whole framebuffer); times->rays and primary_rays count this launch
+ * only.  A set with no row in [0, H) launches nothing and returns RS_OK with zero rays.  Also RS_E_INVALID:
+ * strip_rows no positive multiple of RS_ROW_STRIP, stride < 1, phase outside [0, stride), an unknown
+ * estimator, path == NULL for a path estimator.  After a set with stride > 1 the framebuffer holds only some
+ * rows of the frame: rs_post_frame returns RS_E_UNSUPPORTED until the next render (see
+ * rs_mgpu_render_ground_truth for the gathered form). */
+#define RS_ROW_STRIP 16
+typedef struct { int32_t strip_rows, stride, phase; } rs_row_set;
+#define RS_GT_DIRECT_MIS 0
+#define RS_GT_PATH 1
+#define RS_GT_PATH_UNBIASED 2
+int rs_render_ground_truth_rows(rs_context* ctx, const rs_scene* scene, const rs_camera* camera,
+                                const rs_frame_params* params, int estimator, const rs_path_params* path,
+                                uint32_t frame_index, uint32_t spp, const rs_row_set* rows,
+                                float* frame_rgb_host, rs_pass_times* times);
 
 /* Pass times and rays summed over every frame finished since context creation (or the last reset),
  * without a host sync per frame: each frame records into its own slot of an event ring and the rays
@@ -507,6 +530,21 @@ int rs_mgpu_rebalance_times(const rs_mgpu* m, int round, double* ms);
 int rs_mgpu_render_frame(rs_mgpu* m, const rs_scene* const* scenes, const rs_camera* camera,
                          const rs_frame_params* params, uint32_t frame_index, int gather, float* frame_rgb_host,
                          rs_pass_times* times);
+/* One ground-truth frame (rs_render_ground_truth_rows' estimators) on all ranks: rank r renders the row set
+ * {RS_ROW_STRIP, world, r} on its context's stream -- 16-row strips dealt out round robin, because a ground
+ * truth has no halo to keep bands contiguous for, no earlier frame to balance bands from, and rows whose cost
+ * differs by orders of magnitude (sky rows: one ray; others: spp x up to max_bounces + 1 vertices).  The bands
+ * (rs_mgpu_set_bands / rs_mgpu_rebalance) are neither used nor changed, the ReSTIR history is untouched.
+ * gather != 0: the strips -> global rank 0's framebuffer, rows at their place, one transfer per strip (ascending
+ * on both sides of a pair); rs_mgpu_frame_device_ptr, rs_frame_readback and rs_post_frame on rank 0 then see
+ * the full frame -- bit-identical to one context's -- and frame_rgb_host (rank 0, optional) receives it.  On a
+ * context that holds only its own strips (another rank, gather == 0, world > 1) rs_post_frame returns
+ * RS_E_UNSUPPORTED.  times (optional, synchronous): the first local rank's launch.  rs_mgpu_stats gather_bytes /
+ * gather_ms count these gathers too.  More ranks than strips is allowed: the ranks beyond render nothing. */
+int rs_mgpu_render_ground_truth(rs_mgpu* m, const rs_scene* const* scenes, const rs_camera* camera,
+                                const rs_frame_params* params, int estimator, const rs_path_params* path,
+                                uint32_t frame_index, uint32_t spp, int gather, float* frame_rgb_host,
+                                rs_pass_times* times);
 /* the first local rank's framebuffer (on rank 0 after a gather: the full frame) */
 int rs_mgpu_frame_device_ptr(rs_mgpu* m, const float** dptr);
 int rs_mgpu_reset_history(rs_mgpu* m);

@@ -235,6 +235,10 @@ struct rs_context {
     double2 *post_part = nullptr, *post_out = nullptr;
     uint32_t acc_frames = 0;
     uint64_t post_px = 0;                  // pixels the last rs_post_frame's statistics cover
+    // the framebuffer after a ground-truth render over a row set of stride > 1: kGtStrips holds only this context's
+    // strips (rs_post_frame refuses), kGtGathered every rank's (rs::ctx_frame_gathered: all rows); kGtNone otherwise
+    enum { kGtNone = 0, kGtStrips = 1, kGtGathered = 2 };
+    int gt_rows = kGtNone;
     rs_denoiser* denoiser = nullptr;       // rs_post_frame's RenderParams::denoise (rs_context_set_denoiser)
     std::vector<rs_denoiser*> denoisers;   // every live denoiser created on this context (rs::ctx_track_denoiser)
     // asynchronous framebuffer readback (rs_frame_readback): ticket ring
@@ -1922,6 +1926,7 @@ extern "C" int rs_tile_finish(rs_context* c, const float** band_rgb, rs_pass_tim
     record_traversal_time(c);
     c->r_last = f.rcur;   // reservoirsLastFrame = final buffer (pointer swap, :477)
     c->frames++;
+    c->gt_rows = rs_context::kGtNone;
     f.active = false;
     if (band_rgb) *band_rgb = L.fb + 3 * (size_t)f.F.y0 * c->W;
     if (t) {
@@ -1979,13 +1984,22 @@ extern "C" int rs_render_frame(rs_context* c, const rs_scene* s, const rs_camera
 
 // The ground-truth renders (rs_mis.h, rs_path.h) into the framebuffer: one launch on the context's stream, spp
 // samples per pixel.  Does not touch the ReSTIR history (G-buffers, reservoirs, frame counter).  launch(T, S, F,
-// grid, slot) enqueues the kernel of traversal kind T on c->fr.fs and returns its hipError_t.
+// grid, slot, rows) enqueues the kernel of traversal kind T on c->fr.fs and returns its hipError_t.  `rows` is the
+// row set of the launch (rs_render_ground_truth_rows: the kernels' kRows instantiations), or null for every row
+// (the full-frame entries: the instantiations they always had, which do not read the set).  The grid covers the
+// set's own strips packed (rs_mis.h pixel_of_rows); a set with no row in the frame launches nothing.
+static const rs_row_set kAllRows = {RS_ROW_STRIP, 1, 0};
 template <class Launch>
 static int render_ground_truth(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
-                               uint32_t frame_index, uint32_t spp, float* frame_rgb_host, rs_pass_times* t,
-                               const char* who, Launch&& launch) {
+                               uint32_t frame_index, uint32_t spp, const rs_row_set* rows, float* frame_rgb_host,
+                               rs_pass_times* t, const char* who, Launch&& launch) {
     const std::string fn = who;
     if (!c || !s || !cam || !P) return fail(c, RS_E_INVALID, fn + ": null argument");
+    const rs_row_set rs = rows ? *rows : kAllRows;
+    if (rs.strip_rows < RS_ROW_STRIP || rs.strip_rows % RS_ROW_STRIP != 0)
+        return fail(c, RS_E_INVALID, fn + ": strip_rows must be a positive multiple of RS_ROW_STRIP");
+    if (rs.stride < 1 || rs.phase < 0 || rs.phase >= rs.stride)
+        return fail(c, RS_E_INVALID, fn + ": need stride >= 1 and 0 <= phase < stride");
     if (s->ctx != c) return fail(c, RS_E_INVALID, fn + ": scene belongs to another context");
     if (c->fr.active) return fail(c, RS_E_INVALID, fn + ": a tile frame is in flight");
     if (P->use_skybox && s->sky < 0)
@@ -1997,7 +2011,13 @@ static int render_ground_truth(rs_context* c, const rs_scene* s, const rs_camera
     make_camera(cam, c->H, gc, F.inv_view);
     F.cam = gc; F.camp = gc;
     const DevScene S = s->dev();
-    const dim3 g = grid_rows(c->W, 0, c->H);
+    // the set's own strips p, p + stride, ... of ceil(H / strip_rows): all whole but the frame's last one
+    const int n_strips = (c->H + rs.strip_rows - 1) / rs.strip_rows;
+    const int n_own = rs.phase < n_strips ? (n_strips - 1 - rs.phase) / rs.stride + 1 : 0;
+    int v_rows = n_own * rs.strip_rows;
+    if (n_own && rs.phase + (n_own - 1) * rs.stride == n_strips - 1) v_rows -= n_strips * rs.strip_rows - c->H;
+    const dim3 g = grid_rows(c->W, 0, v_rows);
+    const RowSet R = {rs.strip_rows, rs.stride, rs.phase};
     Frame& f = c->fr;
     f.fs = c->stream; f.li = 0;                   // the context's stream (after every frame enqueued so far), lane 0
     Lane& L = c->lanes[0];
@@ -2011,7 +2031,8 @@ static int render_ground_truth(rs_context* c, const rs_scene* s, const rs_camera
     pick_traversal(c, s);
     f.twide = s->wide_on;
     f.tuning = false;                // the ReSTIR frames own the per-scene traversal tuning
-    HIPCHK(c, with_trav(c, [&](auto T) { return launch(T, S, F, g, count_slot(c, L, g)); }));
+    if (v_rows > 0) HIPCHK(c, with_trav(c, [&](auto T) { return launch(T, S, F, g, count_slot(c, L, g), R); }));
+    c->gt_rows = rs.stride > 1 ? rs_context::kGtStrips : rs_context::kGtNone;
     HIPCHK(c, hipEventRecord(e1, c->stream));
     HIPCHK(c, reduce_counts(c, L, c->stream));
     if (t || frame_rgb_host) {
@@ -2031,38 +2052,46 @@ static int render_ground_truth(rs_context* c, const rs_scene* s, const rs_camera
     return RS_OK;
 }
 
-// MIS direct-light ground truth (rs_mis.h; SURVEY.md §8f-3)
-extern "C" int rs_render_direct_mis(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
-                                    uint32_t frame_index, uint32_t spp, float* frame_rgb_host, rs_pass_times* t) {
-    return render_ground_truth(c, s, cam, P, frame_index, spp, frame_rgb_host, t, "rs_render_direct_mis",
-                               [&](auto T, const DevScene& S, const FrameConst& F, dim3 g, CountSlot slot) {
-        k_direct_mis<T()><<<g, 256, 0, c->fr.fs>>>(S, F, (int)spp, c->lane().fb, slot);
+static int render_direct_mis_with(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                                  uint32_t frame_index, uint32_t spp, const rs_row_set* rows, float* frame_rgb_host,
+                                  rs_pass_times* t, const char* who) {
+    return render_ground_truth(c, s, cam, P, frame_index, spp, rows, frame_rgb_host, t, who,
+                               [&](auto T, const DevScene& S, const FrameConst& F, dim3 g, CountSlot slot, RowSet R) {
+        const auto k = rows ? &k_direct_mis<T(), true> : &k_direct_mis<T(), false>;
+        k<<<g, 256, 0, c->fr.fs>>>(S, F, (int)spp, c->lane().fb, slot, R);
         return hipGetLastError();
     });
 }
 
+// MIS direct-light ground truth (rs_mis.h; SURVEY.md §8f-3)
+extern "C" int rs_render_direct_mis(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                                    uint32_t frame_index, uint32_t spp, float* frame_rgb_host, rs_pass_times* t) {
+    return render_direct_mis_with(c, s, cam, P, frame_index, spp, nullptr, frame_rgb_host, t, "rs_render_direct_mis");
+}
+
 // The two path tracers: rs_render_path's checks, record array and launch, said once.  The vertex records of the
 // paths in flight take (max_bounces + 1) * 8 KiB of dynamic LDS per workgroup: 48 KiB at the default, 128 KiB at the
-// cap.  kernel(T) is the instantiation for traversal kind T; the LDS attribute is that kernel's own.
+// cap.  kernel(T, kRows) is the instantiation for traversal kind T, over a row set or not; the LDS attribute is that
+// kernel's own.
 template <class Kernel>
 static int render_path_with(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
-                            const rs_path_params* pp, uint32_t frame_index, uint32_t spp, float* frame_rgb_host,
-                            rs_pass_times* t, const char* who, Kernel&& kernel) {
+                            const rs_path_params* pp, uint32_t frame_index, uint32_t spp, const rs_row_set* rows,
+                            float* frame_rgb_host, rs_pass_times* t, const char* who, Kernel&& kernel) {
     const std::string fn = who;
     if (!pp) return fail(c, RS_E_INVALID, fn + ": null argument");
     if (pp->max_bounces < 0 || pp->max_bounces > 15)
         return fail(c, RS_E_INVALID, fn + ": max_bounces must be in [0, 15]");
     const PathConst Q = {(int)spp, pp->max_bounces, pp->russian_roulette ? 1 : 0, pp->calc_di ? 1 : 0, pp->calc_gi ? 1 : 0};
     const size_t lds = (size_t)(Q.max_bounces + 1) * kPathRec * kPathBlock * sizeof(float);
-    return render_ground_truth(c, s, cam, P, frame_index, spp, frame_rgb_host, t, who,
-                               [&](auto T, const DevScene& S, const FrameConst& F, dim3 g, CountSlot slot) {
-        const auto k = kernel(T);
+    return render_ground_truth(c, s, cam, P, frame_index, spp, rows, frame_rgb_host, t, who,
+                               [&](auto T, const DevScene& S, const FrameConst& F, dim3 g, CountSlot slot, RowSet R) {
+        const auto k = rows ? kernel(T, std::true_type{}) : kernel(T, std::false_type{});
         if (lds > 64 * 1024) {       // beyond what a launch may ask for unannounced
             const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
         }
-        k<<<g, kPathBlock, lds, c->fr.fs>>>(S, F, Q, c->lane().fb, slot);
+        k<<<g, kPathBlock, lds, c->fr.fs>>>(S, F, Q, c->lane().fb, slot, R);
         return hipGetLastError();
     });
 }
@@ -2071,16 +2100,35 @@ static int render_path_with(rs_context* c, const rs_scene* s, const rs_camera* c
 extern "C" int rs_render_path(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
                               const rs_path_params* pp, uint32_t frame_index, uint32_t spp, float* frame_rgb_host,
                               rs_pass_times* t) {
-    return render_path_with(c, s, cam, P, pp, frame_index, spp, frame_rgb_host, t, "rs_render_path",
-                            [](auto T) { return &k_path<T(), kEstReference>; });
+    return render_path_with(c, s, cam, P, pp, frame_index, spp, nullptr, frame_rgb_host, t, "rs_render_path",
+                            [](auto T, auto R) { return &k_path<T(), kEstReference, R()>; });
 }
 
 // The unbiased NEE + MIS path tracer (rs_path.h, kEstUnbiased)
 extern "C" int rs_render_path_unbiased(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
                                        const rs_path_params* pp, uint32_t frame_index, uint32_t spp,
                                        float* frame_rgb_host, rs_pass_times* t) {
-    return render_path_with(c, s, cam, P, pp, frame_index, spp, frame_rgb_host, t, "rs_render_path_unbiased",
-                            [](auto T) { return &k_path<T(), kEstUnbiased>; });
+    return render_path_with(c, s, cam, P, pp, frame_index, spp, nullptr, frame_rgb_host, t, "rs_render_path_unbiased",
+                            [](auto T, auto R) { return &k_path<T(), kEstUnbiased, R()>; });
+}
+
+// Any of the three over a row set (restir_c.h): the same launch, the set's strips only
+extern "C" int rs_render_ground_truth_rows(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                                           int estimator, const rs_path_params* pp, uint32_t frame_index, uint32_t spp,
+                                           const rs_row_set* rows, float* frame_rgb_host, rs_pass_times* t) {
+    const char* who = "rs_render_ground_truth_rows";
+    if (!rows) return fail(c, RS_E_INVALID, std::string(who) + ": null argument");
+    switch (estimator) {
+    case RS_GT_DIRECT_MIS:
+        return render_direct_mis_with(c, s, cam, P, frame_index, spp, rows, frame_rgb_host, t, who);
+    case RS_GT_PATH:
+        return render_path_with(c, s, cam, P, pp, frame_index, spp, rows, frame_rgb_host, t, who,
+                                [](auto T, auto R) { return &k_path<T(), kEstReference, R()>; });
+    case RS_GT_PATH_UNBIASED:
+        return render_path_with(c, s, cam, P, pp, frame_index, spp, rows, frame_rgb_host, t, who,
+                                [](auto T, auto R) { return &k_path<T(), kEstUnbiased, R()>; });
+    }
+    return fail(c, RS_E_INVALID, std::string(who) + ": unknown estimator");
 }
 
 extern "C" int rs_get_frame_device_ptr(rs_context* c, const float** dptr) {
@@ -2220,7 +2268,11 @@ extern "C" int rs_post_frame(rs_context* c, const rs_post_params* pp, const floa
         HIPCHK(c, hipMalloc(&c->post_out, sizeof(double2)));
     }
     // rows of the last rendered frame / band (rs_render_frame: all rows)
-    const int y0 = c->frames ? c->fr.F.y0 : 0, y1 = c->frames ? c->fr.F.y1 : c->H;
+    if (c->gt_rows == rs_context::kGtStrips)
+        return fail(c, RS_E_UNSUPPORTED, "rs_post_frame: the last render was a ground-truth row set that was not gathered "
+                                         "into this context (rs_mgpu_render_ground_truth with gather, global rank 0)");
+    const bool band = c->frames && c->gt_rows != rs_context::kGtGathered;   // a gathered ground truth: all rows
+    const int y0 = band ? c->fr.F.y0 : 0, y1 = band ? c->fr.F.y1 : c->H;
     // a denoised display is validated before the accumulator blends this frame (a rejected call leaves the
     // accumulator and accFrameCtr as they were)
     if (pp->denoise && !c->denoiser) return fail(c, RS_E_INVALID, "rs_post_frame: denoise without a denoiser (rs_context_set_denoiser)");
@@ -2464,6 +2516,7 @@ void ctx_track_denoiser(rs_context* c, rs_denoiser* d, bool add) {
     if (add) v.push_back(d);
     else if (c->denoiser == d) c->denoiser = nullptr;
 }
+void ctx_frame_gathered(rs_context* c) { c->gt_rows = rs_context::kGtGathered; }
 int ctx_join(rs_context* c, hipStream_t st) {
     HIPCHK(c, enter(c));
     if (st == c->stream) return RS_OK;

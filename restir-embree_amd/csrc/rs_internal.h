@@ -22,6 +22,9 @@ __attribute__((visibility("hidden"))) int ctx_height(const rs_context* c);
 // work enqueued on `st` after the frame (a multi-GPU gather into the frame's framebuffer) becomes part of
 // the frame for everything that orders on the context's stream (readback, post-frame, the next frame)
 __attribute__((visibility("hidden"))) int ctx_join(rs_context* c, hipStream_t st);
+// every rank's strips of a ground-truth render now lie in this context's framebuffer (rs_mgpu_render_ground_truth's
+// gather on global rank 0): rs_post_frame processes all rows
+__attribute__((visibility("hidden"))) void ctx_frame_gathered(rs_context* c);
 // record an error message on the context (rs_last_error) and return `code`
 __attribute__((visibility("hidden"))) int ctx_fail(rs_context* c, int code, const std::string& msg);
 // rs_denoise.hip: the denoiser on device images (float3 rows at `*st` floats per pixel), enqueued on `st`;

@@ -223,12 +223,17 @@ struct rs_mgpu {
     // frame on the context stream, rs_synchronize, an all-reduce on comm[0] -- is ordered after the
     // transfer that reads (senders) or writes (rank 0) this lane's framebuffer.
     int gather(std::vector<GpuRank*>& rk) {
+        const size_t row = (size_t)W * 3 * sizeof(float);
+        return gather_rows(rk, [&](int r) { return mgpu::gather_plan(r, bounds, row); });
+    }
+    // plan_of(global rank) is the rank's gather plan: the bands of a ReSTIR frame, the strips of a ground truth
+    template <class PlanOf>
+    int gather_rows(std::vector<GpuRank*>& rk, PlanOf&& plan_of) {
         if (world == 1) return 0;
         if (int rc = record_all(rk, 2 * kTimedPasses)) return rc;
-        const size_t row = (size_t)W * 3 * sizeof(float);
         std::vector<std::vector<mgpu::Xfer>> plans;
         for (size_t i = 0; i < rk.size(); ++i) {
-            plans.push_back(mgpu::gather_plan(rank_ids[i], bounds, row));
+            plans.push_back(plan_of(rank_ids[i]));
             stats.gather_bytes += mgpu::plan_bytes(plans.back(), false);
         }
         if (!local) {
@@ -389,6 +394,44 @@ extern "C" int rs_mgpu_render_frame(rs_mgpu* m, const rs_scene* const* scenes, c
     if (int rc = mgpu::render_frame(m->rank_ptrs, *m, m->bounds, m->rank_ids, P->do_spatial ? P->spatial_passes : 0,
                                     halo, halo, gather != 0))
         return rc;
+    if (frame_rgb_host && m->rank_ids[0] == 0) {
+        uint64_t t = 0;
+        if (int rc = rs_frame_readback(m->ranks[0].ctx, frame_rgb_host, &t)) return rc;
+        if (int rc = rs_frame_wait(m->ranks[0].ctx, t)) return rc;
+    }
+    return RS_OK;
+}
+
+// A ground truth on all ranks (restir_c.h): every local rank's strips {RS_ROW_STRIP, world, rank} on its context's
+// stream, then the strips -> global rank 0's framebuffer through the gather of the ReSTIR frames (its plans' pairing,
+// its events, its statistics), the strip plan in the band plan's place.
+extern "C" int rs_mgpu_render_ground_truth(rs_mgpu* m, const rs_scene* const* scenes, const rs_camera* cam,
+                                           const rs_frame_params* P, int estimator, const rs_path_params* pp,
+                                           uint32_t frame_index, uint32_t spp, int gather, float* frame_rgb_host,
+                                           rs_pass_times* times) {
+    if (!m || !cam || !P) return RS_E_INVALID;
+    if (int rc = check_scenes(m, scenes)) return rc;
+    static_assert(mgpu::kStripRows == RS_ROW_STRIP, "one strip height");
+    m->rank_ptrs.clear();
+    for (size_t i = 0; i < m->ranks.size(); ++i) {
+        GpuRank& g = m->ranks[i];
+        const rs_row_set rows = {RS_ROW_STRIP, m->world, m->rank_ids[i]};
+        if (int rc = rs_render_ground_truth_rows(g.ctx, scenes[i], cam, P, estimator, pp, frame_index, spp, &rows, nullptr,
+                                                 i == 0 ? times : nullptr))
+            return rc;
+        // the launch ran on the context's stream into its framebuffer: what frame_base() and the gather go by
+        g.st = ctx_stream(g.ctx); g.lane = 0; g.y0 = 0; g.y1 = m->H;
+        if (int rc = rs_get_frame_device_ptr(g.ctx, &g.band)) return rc;
+        m->rank_ptrs.push_back(&g);
+    }
+    if (gather && m->world > 1) {
+        if (int rc = m->begin_frame_stats()) return rc;
+        const size_t row = (size_t)m->W * 3 * sizeof(float);
+        if (int rc = m->gather_rows(m->rank_ptrs, [&](int r) { return mgpu::strip_gather_plan(r, m->world, m->H, row); }))
+            return rc;
+        for (size_t i = 0; i < m->ranks.size(); ++i)
+            if (m->rank_ids[i] == 0) ctx_frame_gathered(m->ranks[i].ctx);
+    }
     if (frame_rgb_host && m->rank_ids[0] == 0) {
         uint64_t t = 0;
         if (int rc = rs_frame_readback(m->ranks[0].ctx, frame_rgb_host, &t)) return rc;

@@ -151,6 +151,29 @@ inline std::vector<Xfer> gather_plan(int r, const std::vector<int>& bounds, size
     }
     return p;
 }
+// ---- ground truths: interleaved strips (rs_mgpu_render_ground_truth).  No halo, no earlier frame to balance
+// from, and row costs between one ray and spp x (max_bounces + 1) vertices per pixel: the rows are dealt out in
+// strips of kStripRows (a workgroup's pixel tile, RS_ROW_STRIP), strip s = rows [16 s, min(16 s + 16, H)) to rank
+// s % world.  Same rule as restir_amd.distributed.strip_rows_of (tests compare the two).
+constexpr int kStripRows = 16;
+struct RowSpan { int y0, y1; };
+// rank r's strips, ascending (none when world exceeds the strip count and r lies beyond it)
+inline std::vector<RowSpan> strip_rows_of(int H, int world, int r) {
+    std::vector<RowSpan> v;
+    for (int y = r * kStripRows; y < H; y += world * kStripRows) v.push_back({y, y + kStripRows < H ? y + kStripRows : H});
+    return v;
+}
+// Gather of the strips into rank 0's full frame: one transfer per strip.  Between two ranks the sends and the
+// receives pair in issue order (RCCL's rule for point-to-point calls of one group) and the last strip may be
+// short, so both sides list a peer's strips in ascending order: rank 0 peer by peer, rank q its own.
+inline std::vector<Xfer> strip_gather_plan(int r, int world, int H, size_t row_bytes) {
+    std::vector<Xfer> p;
+    if (world <= 1) return p;
+    for (int q = r == 0 ? 1 : r; q < (r == 0 ? world : r + 1); ++q)
+        for (const RowSpan& s : strip_rows_of(H, world, q))
+            p.push_back({r == 0 ? q : 0, r != 0, kFrameRows, (size_t)s.y0 * row_bytes, (size_t)(s.y1 - s.y0) * row_bytes});
+    return p;
+}
 // does send `s` of rank `rs` fill recv `x` of rank `rx`?
 inline bool xfer_matches(const Xfer& x, int rx, const Xfer& s, int rs) {
     if (x.send || !s.send || x.peer != rs || s.peer != rx || x.bytes != s.bytes) return false;

@@ -24,6 +24,26 @@ constexpr int kEstReference = 0, kEstUnbiased = 1;
 
 struct MisSurf { vec3 pos, n, wr, kd, ks; float shin, i_m, maxD, maxS, pf; bool phong; };
 
+// The rows of a ground-truth launch (rs_row_set): image rows y with (y / strip_rows) % stride == phase, strip_rows a
+// multiple of the workgroup tile's 16 rows.  The launch covers them packed as virtual rows v = 0, 1, ...: a
+// workgroup's 16 virtual rows lie in one strip, so the strip and the image row of its first virtual row are
+// wave-uniform (scalar registers, computed once); {16, 1, 0} is every row at its place, the full frame.
+struct RowSet { int strip_rows, stride, phase; };
+
+// pixel_of over a row set: whether the pixel exists; x / y clamped into the image as pixel_of clamps them
+__device__ __forceinline__ bool pixel_of_rows(const FrameConst& F, const RowSet& R, int& x, int& y) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int v0 = (int)blockIdx.y * 16;                              // the workgroup's first virtual row
+    const int s = v0 / R.strip_rows;                                  // its strip among the set's own
+    const int y0 = (s * R.stride + R.phase) * R.strip_rows + (v0 - s * R.strip_rows);
+    x = (int)blockIdx.x * 16 + (wave & 1) * 8 + (lane & 7);
+    y = y0 + (wave >> 1) * 8 + (lane >> 3);
+    const bool in = x < F.W && y < F.H;
+    x = x < F.W ? x : F.W - 1;
+    y = y < F.H ? y : F.H - 1;
+    return in;
+}
+
 // DirectMISIntegrator::powerHeuristic (pg/DirectMISIntegrator.cpp:10-15)
 __device__ __forceinline__ float mis_power(float pdf, float other) {
     float a = pdf * pdf, b = other * other;
@@ -159,10 +179,16 @@ __device__ __forceinline__ vec3 mis_light_part(const DevScene& S, const FrameCon
     return dvs(((E.le * w) * mis_brdf(h, lp)) * G, light_pdf);
 }
 
-template <int T>
-__global__ void __launch_bounds__(256) k_direct_mis(DevScene S, FrameConst F, int spp, float* fb, CountSlot C) {
+// kRows: the launch covers the row set R (rs_render_ground_truth_rows); else rows [F.y0, F.y1) and R is not read --
+// the full-frame entries keep the instantiation they had (through the row-set form the reference's
+// path tracer measured 0.8-1.1 % slower at equal registers)
+template <int T, bool kRows = false>
+__global__ void __launch_bounds__(256) k_direct_mis(DevScene S, FrameConst F, int spp, float* fb, CountSlot C,
+                                                        RowSet R) {
     int x, y;
-    const bool in = pixel_of(F, F.y0, F.y1, x, y);
+    bool in;
+    if constexpr (kRows) in = pixel_of_rows(F, R, x, y);
+    else in = pixel_of(F, F.y0, F.y1, x, y);
     const uint64_t t0 = wave_clock();
     const uint32_t pix = (uint32_t)y * (uint32_t)F.W + (uint32_t)x;
     uint32_t rays = in ? 1u : 0u;

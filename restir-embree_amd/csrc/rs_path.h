@@ -50,8 +50,9 @@ __device__ __forceinline__ MisSurf path_surf(const DevScene& S, const SurfHit& h
     return h;
 }
 
-template <int T, int E>
-__global__ void __launch_bounds__(kPathBlock) k_path(DevScene S, FrameConst F, PathConst Q, float* fb, CountSlot C) {
+template <int T, int E, bool kRows = false>                         // kRows: as k_direct_mis's
+__global__ void __launch_bounds__(kPathBlock) k_path(DevScene S, FrameConst F, PathConst Q, float* fb, CountSlot C,
+                                                       RowSet R) {
     // E = kEstReference restates the reference's estimator bit for bit, three biases included.
     // E = kEstUnbiased is the textbook estimator over the same material model, free of the reference's structure: per
     // vertex one light sample with its shadow ray (mis_light_part, unchanged) and one BRDF sample whose ray does both
@@ -69,7 +70,9 @@ __global__ void __launch_bounds__(kPathBlock) k_path(DevScene S, FrameConst F, P
     constexpr int TL = T | TRAV_LANE;               // past the camera vertex every ray is incoherent
     float* const rec = path_rec + threadIdx.x;
     int x, y;
-    const bool in = pixel_of(F, F.y0, F.y1, x, y);
+    bool in;                                                         // y: the image row -- pix, the RNG key, the store
+    if constexpr (kRows) in = pixel_of_rows(F, R, x, y);
+    else in = pixel_of(F, F.y0, F.y1, x, y);
     const uint64_t t0 = wave_clock();
     const uint32_t pix = (uint32_t)y * (uint32_t)F.W + (uint32_t)x;
     uint32_t rays = in ? 1u : 0u;

@@ -45,6 +45,16 @@ def band_rows(H: int, rank: int, world: int):
     return (rank * H) // world, ((rank + 1) * H) // world
 
 
+STRIP_ROWS = 16           # the strip height of a multi-rank ground truth (restir_c.h RS_ROW_STRIP)
+
+
+def strip_rows_of(H: int, rank: int, world: int):
+    """The [y0, y1) strips of `rank` for a ground truth on `world` ranks, ascending: strip s = rows
+    [16 s, min(16 s + 16, H)) belongs to rank s % world (rs_mgpu_core.h strip_rows_of; tests compare the two).
+    Empty when the frame has fewer strips than ranks and `rank` lies beyond them."""
+    return [(y, min(y + STRIP_ROWS, H)) for y in range(rank * STRIP_ROWS, H, world * STRIP_ROWS)]
+
+
 def halo_rows(params) -> int:
     if not params.do_spatial or params.spatial_passes <= 0:
         return 0
@@ -137,6 +147,18 @@ class GpuTileBackend:
             self._sync_if_foreign_stream()
         n = (self.y1 - self.y0) * self.r.W * 3
         return self._view(ptr, n * 4, "<f4", 4)
+
+    def render_ground_truth_rows(self, scene, camera, params, frame_index, spp, path_kwargs, rows):
+        """The rows of the set (strip_rows, stride, phase) of a ground-truth frame, in a full-frame-sized (H * W * 3)
+        tensor over the context's framebuffer; path_kwargs None: the MIS direct-light ground truth, else
+        Renderer.render_path's keywords (max_bounces, ..., unbiased)."""
+        if path_kwargs is None:
+            self.r.render_direct_mis(scene, camera, params, frame_index, spp, copy_out=False, rows=rows)
+        else:
+            self.r.render_path(scene, camera, params, frame_index, spp, copy_out=False, rows=rows, **path_kwargs)
+        self._lane_stream = None               # the launch ran on the context's stream
+        self._sync_if_foreign_stream()
+        return self._view(self.r.frame_device_ptr(), self.r.H * self.r.W * 12, "<f4", 4)
 
     @property
     def last_times(self):
@@ -374,4 +396,50 @@ class TiledRenderer:
         else:
             for w in works:
                 w.wait()
+        return self.frame
+
+    # ---- ground truths: interleaved 16-row strips (strip_rows_of), no halo, no bands
+    def render_path(self, scene, camera, params, frame_index: int, spp: int = 1, max_bounces: int = 5,
+                    russian_roulette: bool = True, calc_di: bool = True, calc_gi: bool = True, unbiased: bool = False,
+                    gather: bool = True):
+        """One path-traced ground-truth frame (Renderer.render_path) across the ranks: this rank renders the strips
+        strip_rows_of(H, rank, world); with gather the full (H, W, 3) frame is returned on rank 0, bit for bit a
+        single renderer's (None elsewhere).  Without gather: this rank's full-frame-sized tensor, its strips valid."""
+        kw = dict(max_bounces=max_bounces, russian_roulette=russian_roulette, calc_di=calc_di, calc_gi=calc_gi,
+                  unbiased=unbiased)
+        return self._ground_truth(scene, camera, params, frame_index, spp, kw, gather)
+
+    def render_direct_mis(self, scene, camera, params, frame_index: int, spp: int = 1, gather: bool = True):
+        """The MIS direct-light ground truth (Renderer.render_direct_mis) the same way."""
+        return self._ground_truth(scene, camera, params, frame_index, spp, None, gather)
+
+    def _ground_truth(self, scene, camera, params, frame_index, spp, path_kwargs, gather):
+        self.wait()                                # lane 0's framebuffer may still feed a ReSTIR frame's gather
+        own = self.be.render_ground_truth_rows(scene, camera, params, frame_index, spp, path_kwargs,
+                                               (STRIP_ROWS, self.world, self.rank))
+        if not gather:
+            return own
+        return self._gather_strips(own)
+
+    def _gather_strips(self, own):
+        """Strips -> rank 0's full frame: one batched P2P group, one op per strip, each peer's strips in ascending
+        order on both sides (a pair's sends and receives match in issue order and the last strip may be short)."""
+        import torch.distributed as dist
+        if self.world == 1:
+            self.frame = own.reshape(self.H, self.W, 3)
+            return self.frame
+        staged = self._staged(own)
+        row = self.W * 3
+        grp = self.lane_groups[0]
+        if self.rank == 0:
+            out = own.cpu() if staged else own     # rank 0's own strips are in place already
+            ops = [dist.P2POp(dist.irecv, out[a * row:b * row], r, grp)
+                   for r in range(1, self.world) for a, b in strip_rows_of(self.H, r, self.world)]
+        else:
+            out = None
+            ops = [dist.P2POp(dist.isend, own[a * row:b * row].cpu() if staged else own[a * row:b * row], 0, grp)
+                   for a, b in strip_rows_of(self.H, self.rank, self.world)]
+        for w in (dist.batch_isend_irecv(ops) if ops else []):
+            w.wait()
+        self.frame = out.reshape(self.H, self.W, 3) if out is not None else None
         return self.frame

@@ -15,7 +15,9 @@ import ctypes
 
 import numpy as np
 
-from .renderer import CameraDesc, PassTimes, RestirError, camera_desc, load_library
+from .params import PathParams
+from .renderer import (CameraDesc, GT_DIRECT_MIS, GT_PATH, GT_PATH_UNBIASED, PassTimes, RestirError, camera_desc,
+                       load_library)
 
 ID_BYTES = 128
 DEFAULT_REFINE = 2        # rs_mgpu_rebalance's time-based refinement rounds unless the caller says otherwise
@@ -114,6 +116,35 @@ class MultiGpuFrame:
             out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if out is not None else None,
             ctypes.byref(self.last_times) if timed else None))
         return out
+
+    def _ground_truth(self, scenes, camera, params, estimator, pp, frame_index, spp, gather, copy_out, timed):
+        cam = camera_desc(camera)
+        out = np.empty((self.H, self.W, 3), np.float32) if copy_out else None
+        self._check(self.lib.rs_mgpu_render_ground_truth(
+            self.h, self._scenes(scenes), ctypes.byref(cam), ctypes.byref(params), int(estimator),
+            ctypes.byref(pp) if pp is not None else None, int(frame_index), int(spp), 1 if gather else 0,
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if out is not None else None,
+            ctypes.byref(self.last_times) if timed else None))
+        return out
+
+    def render_path(self, scenes, camera, params, frame_index: int, spp: int = 1, max_bounces: int = 5,
+                    russian_roulette: bool = True, calc_di: bool = True, calc_gi: bool = True, unbiased: bool = False,
+                    gather: bool = True, copy_out: bool = False, timed: bool = False):
+        """One path-traced ground-truth frame on all ranks (rs_mgpu_render_ground_truth): rank r renders the 16-row
+        strips r, r + world, ...; with gather they land in rank 0's framebuffer, bit for bit one context's
+        Renderer.render_path frame, and post_frame on rank 0's renderer processes all rows.  copy_out (rank 0)
+        returns the (H, W, 3) frame (synchronous)."""
+        pp = PathParams(max_bounces, russian_roulette, calc_di, calc_gi)
+        return self._ground_truth(scenes, camera, params, GT_PATH_UNBIASED if unbiased else GT_PATH, pp, frame_index,
+                                  spp, gather, copy_out, timed)
+
+    def render_direct_mis(self, scenes, camera, params, frame_index: int, spp: int = 1, unbiased: bool = False,
+                          gather: bool = True, copy_out: bool = False, timed: bool = False):
+        """The MIS direct-light ground truth the same way (unbiased: render_path(unbiased=True, calc_gi=False))."""
+        if unbiased:
+            return self.render_path(scenes, camera, params, frame_index, spp, calc_gi=False, unbiased=True,
+                                    gather=gather, copy_out=copy_out, timed=timed)
+        return self._ground_truth(scenes, camera, params, GT_DIRECT_MIS, None, frame_index, spp, gather, copy_out, timed)
 
     def frame_device_ptr(self) -> int:
         p = ctypes.c_void_p()

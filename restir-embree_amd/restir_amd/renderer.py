@@ -42,7 +42,18 @@ EXPORTED_SYMBOLS = [
     "rs_denoiser_execute", "rs_denoise_frame", "rs_context_set_denoiser", "rs_denoiser_set_timing",
     "rs_denoiser_last_ms", "rs_denoiser_layer_ms", "rs_denoiser_get_scale", "rs_denoiser_dump", "rs_denoiser_destroy",
     "rs_render_path", "rs_debug_bvh_tree", "rs_debug_light_tables", "rs_render_path_unbiased",
+    "rs_render_ground_truth_rows", "rs_mgpu_render_ground_truth",
 ]
+
+# ground-truth estimators and the strip height of their row sets (include/restir_c.h RS_GT_*, RS_ROW_STRIP)
+GT_DIRECT_MIS, GT_PATH, GT_PATH_UNBIASED = 0, 1, 2
+ROW_STRIP = 16
+
+
+class RowSet(ctypes.Structure):
+    """rs_row_set: the rows y with (y // strip_rows) % stride == phase"""
+    _fields_ = [("strip_rows", ctypes.c_int32), ("stride", ctypes.c_int32), ("phase", ctypes.c_int32)]
+
 
 # BVH traversal kinds (include/restir_c.h RS_TRAVERSAL_*)
 TRAVERSAL_AUTO, TRAVERSAL_LOCKSTEP, TRAVERSAL_LANE = -1, 0, 1
@@ -211,6 +222,9 @@ def load_library(path: str = LIB_PATH):
     L.rs_render_path.argtypes = [vp, vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(FrameParams),
                                  ctypes.POINTER(PathParams), u32, u32, fp, ctypes.POINTER(PassTimes)]
     L.rs_render_path_unbiased.argtypes = L.rs_render_path.argtypes
+    L.rs_render_ground_truth_rows.argtypes = [vp, vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(FrameParams), i32,
+                                              ctypes.POINTER(PathParams), u32, u32, ctypes.POINTER(RowSet), fp,
+                                              ctypes.POINTER(PassTimes)]
     L.rs_frame_readback.argtypes = [vp, fp, ctypes.POINTER(ctypes.c_uint64)]
     L.rs_frame_wait.argtypes = [vp, ctypes.c_uint64]
     L.rs_host_alloc.argtypes = [vp, ctypes.c_size_t, ctypes.POINTER(vp)]
@@ -229,6 +243,9 @@ def load_library(path: str = LIB_PATH):
                                     u32, i32, i32]
     L.rs_mgpu_render_frame.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(CameraDesc), ctypes.POINTER(FrameParams),
                                        u32, i32, fp, ctypes.POINTER(PassTimes)]
+    L.rs_mgpu_render_ground_truth.argtypes = [vp, ctypes.POINTER(vp), ctypes.POINTER(CameraDesc),
+                                              ctypes.POINTER(FrameParams), i32, ctypes.POINTER(PathParams), u32, u32, i32,
+                                              fp, ctypes.POINTER(PassTimes)]
     L.rs_mgpu_frame_device_ptr.argtypes = [vp, ctypes.POINTER(vp)]
     L.rs_mgpu_reset_history.argtypes = [vp]
     L.rs_mgpu_allreduce.argtypes = [vp, ctypes.POINTER(ctypes.c_double), i32, i32]
@@ -625,14 +642,18 @@ class Renderer:
         return out
 
     def render_direct_mis(self, scene: Scene, camera, params: FrameParams, frame_index: int = 0, spp: int = 1,
-                          copy_out: bool = True, timed: bool = False, unbiased: bool = False) -> np.ndarray | None:
+                          copy_out: bool = True, timed: bool = False, unbiased: bool = False,
+                          rows=None) -> np.ndarray | None:
         """MIS direct-light ground truth (rs_render_direct_mis; DirectMISIntegrator, calcGI off): spp
         samples per pixel into the framebuffer.  Accumulate frames with post_frame(accumulate=True) for a
         converged reference.  timed=True fills last_times (shade_ms = the launch, rays).  unbiased=True: the
-        unbiased estimator's direct light instead (render_path(unbiased=True, calc_gi=False))."""
+        unbiased estimator's direct light instead (render_path(unbiased=True, calc_gi=False)).  rows: as
+        render_path's."""
         if unbiased:
             return self.render_path(scene, camera, params, frame_index, spp, calc_gi=False, copy_out=copy_out,
-                                    timed=timed, unbiased=True)
+                                    timed=timed, unbiased=True, rows=rows)
+        if rows is not None:
+            return self._render_rows(scene, camera, params, GT_DIRECT_MIS, None, frame_index, spp, rows, copy_out, timed)
         cam = camera_desc(camera)
         out = self.frame_data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if copy_out else None
         self._check(self.lib.rs_render_direct_mis(self.h, scene.h, ctypes.byref(cam), ctypes.byref(params),
@@ -642,19 +663,35 @@ class Renderer:
 
     def render_path(self, scene: Scene, camera, params: FrameParams, frame_index: int = 0, spp: int = 1,
                     max_bounces: int = 5, russian_roulette: bool = True, calc_di: bool = True, calc_gi: bool = True,
-                    copy_out: bool = True, timed: bool = False, unbiased: bool = False) -> np.ndarray | None:
+                    copy_out: bool = True, timed: bool = False, unbiased: bool = False,
+                    rows=None) -> np.ndarray | None:
         """NEE path tracer (rs_render_path; NEEPathIntegrator::integrateImpl2 with the MIS direct integrator):
         direct plus indirect light up to max_bounces, spp samples per pixel into the framebuffer.  calc_gi=False
         is render_direct_mis bit for bit.  Accumulate frames with post_frame(accumulate=True).  timed=True fills
         last_times (shade_ms = the launch, rays).  unbiased=True: rs_render_path_unbiased, the textbook NEE + MIS
         estimator over the same material model -- the reference's estimator is dark on materials with kd and ks;
-        params.normal_offset is not used by it."""
-        cam = camera_desc(camera)
+        params.normal_offset is not used by it.  rows=(strip_rows, stride, phase): rs_render_ground_truth_rows --
+        only the rows y with (y // strip_rows) % stride == phase are rendered, bit for bit the full frame's, and the
+        other rows of the framebuffer keep their contents."""
         pp = PathParams(max_bounces, russian_roulette, calc_di, calc_gi)
+        if rows is not None:
+            return self._render_rows(scene, camera, params, GT_PATH_UNBIASED if unbiased else GT_PATH, pp, frame_index,
+                                     spp, rows, copy_out, timed)
+        cam = camera_desc(camera)
         out = self.frame_data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if copy_out else None
         fn = self.lib.rs_render_path_unbiased if unbiased else self.lib.rs_render_path
         self._check(fn(self.h, scene.h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(pp),
                        int(frame_index), int(spp), out, ctypes.byref(self.last_times) if timed else None))
+        return self.frame_data if copy_out else None
+
+    def _render_rows(self, scene, camera, params, estimator, pp, frame_index, spp, rows, copy_out, timed):
+        cam = camera_desc(camera)
+        rs = RowSet(*[int(v) for v in rows])
+        out = self.frame_data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if copy_out else None
+        self._check(self.lib.rs_render_ground_truth_rows(
+            self.h, scene.h, ctypes.byref(cam), ctypes.byref(params), int(estimator),
+            ctypes.byref(pp) if pp is not None else None, int(frame_index), int(spp), ctypes.byref(rs), out,
+            ctypes.byref(self.last_times) if timed else None))
         return self.frame_data if copy_out else None
 
     def debug_trace(self, scene: Scene, o, d, tnear, tfar, any_hit: bool, lockstep: bool = True,

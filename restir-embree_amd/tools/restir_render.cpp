@@ -16,6 +16,8 @@
 // --ranks N: the frames as N row bands, one context per rank (HIP device rank % device count) driven from
 // this thread through rs_mgpu_create_local / rs_mgpu_render_frame (halo exchange + gather by device
 // copies); --compare also renders them on one context and reports whether every frame is bit-identical.
+// With --path SPP the N ranks render the path tracer's frames instead (rs_mgpu_render_ground_truth: 16-row strips
+// dealt out round robin, gathered on rank 0); same JSON line.
 #include "../../include/restir.hpp"
 
 #include <algorithm>
@@ -113,18 +115,26 @@ int main(int argc, char** argv) {
             mg.camera_ = mg.rank(0).camera_;
             if (cam_set) mg.camera_ = restir::Camera(eye[0], eye[1], eye[2], at[0], at[1], at[2], fov);
             mg.params = prm;
+            mg.samplesPerPixel = (uint32_t)std::max(path_spp, 1);
+            mg.pathParams.max_bounces = bounces;
+            mg.unbiasedEstimator = unbiased;
+            // one frame of either renderer: the ReSTIR frame, or with --path the ground truth
+            auto produce = [&](auto& r) { if (path_spp > 0) r.produceStandard(); else r.produceRestir(); };
             std::unique_ptr<restir::Renderer> one;
             if (compare) {
                 one.reset(new restir::Renderer(W, H));
                 load(*one);
                 one->camera_ = mg.camera_;
                 one->params = prm;
+                one->samplesPerPixel = mg.samplesPerPixel;
+                one->pathParams = mg.pathParams;
+                one->unbiasedEstimator = unbiased;
             }
             bool same = true;
             for (int f = 0; f < frames; ++f) {
-                mg.produceRestir();
+                produce(mg);
                 if (one) {
-                    one->produceRestir();
+                    produce(*one);
                     same = same && std::memcmp(one->frame_data(), mg.frame_data(), (size_t)W * H * 12) == 0;
                 }
             }
