@@ -81,17 +81,37 @@ typedef struct {
     float fov_y_deg;
 } rs_camera;
 
+/* The largest confidence_cap.  Confidences are ints, and a merge adds those of its inputs before it caps the sum:
+ * a spatial merge those of the pixel and of up to 64 neighbours, a temporal merge those of the current and of the
+ * previous reservoir.  Every stored confidence has passed a cap (the initial pass caps m_area + m_brdf, history was
+ * capped by the frame that wrote it), so with every accepted cap <= floor(INT32_MAX / 65) = 33 038 209 no sum
+ * exceeds 65 * cap <= INT32_MAX.  (The reference's slider runs from 1 to 150, pg/ReSTIRIntegrator.cpp:43.) */
+#define RS_MAX_CONFIDENCE_CAP 33038209
+/* The largest spatial_radius, 2^56.  A neighbour's offset is (int)(sqrtf(R * u) * cos) with u < 1: its magnitude is
+ * below 2^28 * (1 + a few ulp), so the conversion to int is defined and x + offset, with 0 <= x < 2^30 (the largest
+ * frame side rs_context_create takes), stays inside (-2^29, 2^30 + 2^29).  The halo of a tile is floor(sqrtf(R))
+ * <= 2^28 rows.  (The reference's slider runs from 0 to 2048, pg/ReSTIRIntegrator.cpp:49.) */
+#define RS_MAX_SPATIAL_RADIUS 72057594037927936.0f
+
 /* POD snapshot of ReSTIRIntegrator's static knobs (pg/ReSTIRIntegrator.cpp:13-35) and of its private
- * RenderParams (pg/RenderParams.h:5-17), passed by value per frame. */
+ * RenderParams (pg/RenderParams.h:5-17), passed by value per frame.  A frame whose confidence_cap or spatial_radius
+ * lies outside its range is rejected with RS_E_INVALID before anything is launched (rs_render_frame, rs_tile_begin,
+ * rs_mgpu_render_frame); the context's history stays as it was. */
 typedef struct {
     int32_t m_area;                /* M_Area */
     int32_t m_brdf;                /* M_Brdf */
     int32_t spatial_neighbors;     /* spatialReuseNeighborCount (k) */
     int32_t spatial_passes;        /* spatialPassCount (P) */
-    int32_t confidence_cap;        /* confidenceCap */
-    float spatial_radius;          /* spatialReuseRadius (R) */
-    float min_normal_similarity;
-    float max_depth_difference;
+    int32_t confidence_cap;        /* confidenceCap: 0 .. RS_MAX_CONFIDENCE_CAP */
+    float spatial_radius;          /* spatialReuseRadius (R), pixels squared: 0 .. RS_MAX_SPATIAL_RADIUS, not NaN.
+                                      Neighbours lie up to floor(sqrtf(R)) pixels away (0 for R < 1: the pixel
+                                      itself); offsets beyond the frame are clamped to its border */
+    float min_normal_similarity;   /* reject_dissimilar: a neighbour with dot(n, n') < this is rejected.  Any float:
+                                      <= -1 rejects nothing, > 1 everything; NaN rejects nothing (the comparison
+                                      is false) */
+    float max_depth_difference;    /* reject_dissimilar: a neighbour whose depth ratio lies outside 1 -+ this / 2 is
+                                      rejected.  Any float: negative rejects every neighbour, +inf and NaN none
+                                      (both comparisons are false) */
     int32_t do_spatial;
     int32_t do_temporal;
     int32_t do_visibility_pass;

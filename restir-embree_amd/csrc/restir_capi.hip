@@ -370,6 +370,9 @@ static Switches read_switches() {
 }
 extern "C" int rs_context_create(int hip_device, int width, int height, void* hip_stream, rs_context** out) {
     if (!out || width <= 0 || height <= 0) return fail(nullptr, RS_E_INVALID, "rs_context_create: bad arguments");
+    // pixel coordinates plus a neighbour offset stay ints (restir_c.h RS_MAX_SPATIAL_RADIUS)
+    if (width > (1 << 30) || height > (1 << 30))
+        return fail(nullptr, RS_E_INVALID, "rs_context_create: width and height must not exceed 2^30");
     *out = nullptr;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
@@ -1542,6 +1545,25 @@ static bool ensure_handoff(rs_context* c, Lane& L, size_t slots) {
     return true;
 }
 
+// The ranges of the frame parameters that need neither the scene nor the tile (rs_internal.h: rs_mgpu_render_frame
+// asks before it touches a rank).
+namespace rs {
+int check_frame_params(rs_context* c, const rs_frame_params* P) {
+    if (P->m_area < 0 || P->m_brdf < 0 || P->spatial_passes < 0 || P->confidence_cap < 0)
+        return fail(c, RS_E_INVALID, "rs_frame_params: negative count");
+    // 65 capped confidences (a spatial merge's) sum in an int: restir_c.h RS_MAX_CONFIDENCE_CAP
+    static_assert(65ll * RS_MAX_CONFIDENCE_CAP <= INT32_MAX && 65ll * (RS_MAX_CONFIDENCE_CAP + 1ll) > INT32_MAX, "cap");
+    if (P->confidence_cap > RS_MAX_CONFIDENCE_CAP)
+        return fail(c, RS_E_INVALID, "rs_frame_params: confidence_cap must be in [0, RS_MAX_CONFIDENCE_CAP = 33038209]");
+    // neighbor_px forms (int)(sqrtf(radius * u) * cos) and x + it: restir_c.h RS_MAX_SPATIAL_RADIUS; !(>= 0) is NaN too
+    if (!(P->spatial_radius >= 0.0f) || P->spatial_radius > RS_MAX_SPATIAL_RADIUS)
+        return fail(c, RS_E_INVALID, "rs_frame_params: spatial_radius must be in [0, RS_MAX_SPATIAL_RADIUS = 2^56] and not NaN");
+    if (P->do_spatial && (P->spatial_neighbors < 0 || P->spatial_neighbors > 64))
+        return fail(c, RS_E_INVALID, "rs_frame_params: spatial_neighbors must be in [0, 64]");
+    if (P->spatial_mis < 0 || P->spatial_mis > 4) return fail(c, RS_E_INVALID, "rs_frame_params: bad spatial_mis");
+    return RS_OK;
+}
+}  // namespace rs
 // ---- rs_tile_begin, step by step
 static int check_frame_args(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
                             const rs_tile_desc* tile) {
@@ -1549,11 +1571,7 @@ static int check_frame_args(rs_context* c, const rs_scene* s, const rs_camera* c
     if (s->ctx != c) return fail(c, RS_E_INVALID, "rs_tile_begin: scene belongs to another context");
     if (P->use_skybox && s->sky < 0)
         return fail(c, RS_E_UNSUPPORTED, "use_skybox: the scene has no sky map (rs_scene_set_sky / rs_scene_load_sky)");
-    if (P->m_area < 0 || P->m_brdf < 0 || P->spatial_passes < 0 || P->confidence_cap < 0)
-        return fail(c, RS_E_INVALID, "rs_frame_params: negative count");
-    if (P->do_spatial && (P->spatial_neighbors < 0 || P->spatial_neighbors > 64))
-        return fail(c, RS_E_INVALID, "rs_frame_params: spatial_neighbors must be in [0, 64]");
-    if (P->spatial_mis < 0 || P->spatial_mis > 4) return fail(c, RS_E_INVALID, "rs_frame_params: bad spatial_mis");
+    if (int rc = rs::check_frame_params(c, P)) return rc;
     if (P->debug_reprojection && (tile->y0 != 0 || tile->y1 != c->H))
         return fail(c, RS_E_UNSUPPORTED, "debug_reprojection: full frames only (its marks land on any pixel)");
     if (tile->y0 < 0 || tile->y1 > c->H || tile->y0 >= tile->y1 || tile->margin < 0 || tile->halo < 0 ||

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <string>
 
+#include "../../include/restir_c.h"
+
 struct rs_context;
 struct rs_denoiser;
 
@@ -27,6 +29,10 @@ __attribute__((visibility("hidden"))) int ctx_join(rs_context* c, hipStream_t st
 __attribute__((visibility("hidden"))) void ctx_frame_gathered(rs_context* c);
 // record an error message on the context (rs_last_error) and return `code`
 __attribute__((visibility("hidden"))) int ctx_fail(rs_context* c, int code, const std::string& msg);
+// the ranges of a frame's parameters (restir_c.h: counts, confidence_cap, spatial_radius, spatial_neighbors,
+// spatial_mis): RS_OK, or RS_E_INVALID with the message on `c`.  rs_tile_begin's first step; rs_mgpu_render_frame
+// asks before it touches any rank, so a rejected frame leaves no rank begun and no statistics counted.
+__attribute__((visibility("hidden"))) int check_frame_params(rs_context* c, const rs_frame_params* P);
 // rs_denoise.hip: the denoiser on device images (float3 rows at `*st` floats per pixel), enqueued on `st`;
 // input_scale <= 0 / NaN: auto-exposure.  The output buffer rs_denoise_frame writes; the owning context.
 __attribute__((visibility("hidden"))) int denoise_run(rs_denoiser* d, hipStream_t st, const float* color, int cst,

@@ -376,6 +376,9 @@ extern "C" int rs_mgpu_render_frame(rs_mgpu* m, const rs_scene* const* scenes, c
                                     rs_pass_times* times) {
     if (!m || !cam || !P) return RS_E_INVALID;
     if (int rc = check_scenes(m, scenes)) return rc;
+    // every rank's rs_tile_begin would refuse the same parameters: ask first, with no rank begun and nothing counted
+    if (int rc = check_frame_params(m->ranks.empty() ? nullptr : m->ranks[0].ctx, P)) return rc;
+    static_assert(mgpu::kMaxSpatialRadius == RS_MAX_SPATIAL_RADIUS, "rs_mgpu_core.h and restir_c.h: one radius range");
     const int halo = m->world > 1 ? mgpu::halo_rows(P->spatial_radius, P->do_spatial && P->spatial_passes > 0) : 0;
     for (int r = 0; r < m->world; ++r)
         if (halo && m->bounds[r + 1] - m->bounds[r] < halo)

@@ -26,11 +26,15 @@
 namespace rs {
 namespace mgpu {
 
-// halo rows for a spatial radius, float32 semantics as the device forms the offset
+// the largest spatial radius of a frame, 2^56 (restir_c.h RS_MAX_SPATIAL_RADIUS; rs_mgpu.hip asserts them equal)
+constexpr float kMaxSpatialRadius = 72057594037927936.0f;
+// halo rows for a spatial radius, float32 semantics as the device forms the offset.  The domain is the frame
+// parameter's, [0, kMaxSpatialRadius]: at most 2^28 rows.  -1 for a radius outside it (negative, NaN, larger), which
+// no frame is rendered with; restir_amd.distributed.halo_rows raises ValueError there.
 inline int halo_rows(float radius, bool spatial) {
     if (!spatial) return 0;
-    const float r = radius > 0.0f ? radius : 0.0f;
-    return (int)std::floor(std::sqrt(r));     // std::sqrt(float): correctly rounded like sqrtf
+    if (!(radius >= 0.0f) || radius > kMaxSpatialRadius) return -1;
+    return (int)std::floor(std::sqrt(radius));     // std::sqrt(float): correctly rounded like sqrtf
 }
 
 // equal row bands: rank r gets [r*H/world, (r+1)*H/world)

@@ -40,6 +40,8 @@ import ctypes
 
 import numpy as np
 
+from .params import MAX_SPATIAL_RADIUS
+
 
 def band_rows(H: int, rank: int, world: int):
     return (rank * H) // world, ((rank + 1) * H) // world
@@ -60,7 +62,11 @@ def halo_rows(params) -> int:
         return 0
     # float32 semantics, as the device forms the offset (trunc(sqrtf(U(0,R)) * cos)): for R just below a
     # perfect square (24.999998f) sqrtf rounds to 5.0 where a float64 sqrt would give a 4-row halo
-    r = np.float32(max(0.0, float(params.spatial_radius)))
+    # The domain is the frame parameter's (params.MAX_SPATIAL_RADIUS; rs_mgpu_core.h halo_rows returns -1 outside it):
+    # a negative, NaN or larger radius is no frame's, and the library rejects it before anything is launched.
+    r = np.float32(params.spatial_radius)
+    if not (r >= 0.0) or r > MAX_SPATIAL_RADIUS:
+        raise ValueError(f"spatial_radius {float(r)!r} is outside [0, 2^56]")
     return int(np.floor(np.sqrt(r, dtype=np.float32)))
 
 

@@ -15,6 +15,11 @@ CONSTANT, CONSTANT_DEBIAS_CONTRIB, CONSTANT_DEBIAS_Z_TERM, BALANCE_HEURISTIC, PA
 MIS_NAMES = {"constant": CONSTANT, "debias_contrib": CONSTANT_DEBIAS_CONTRIB, "debias_z": CONSTANT_DEBIAS_Z_TERM,
              "balance": BALANCE_HEURISTIC, "pairwise": PAIRWISE_MIS}
 
+# The ranges of confidence_cap and spatial_radius (include/restir_c.h RS_MAX_CONFIDENCE_CAP, RS_MAX_SPATIAL_RADIUS;
+# tests pin the values equal): a frame outside them is rejected with RS_E_INVALID before anything is launched.
+MAX_CONFIDENCE_CAP = (2**31 - 1) // 65        # 33 038 209: a spatial merge sums up to 65 capped confidences in an int
+MAX_SPATIAL_RADIUS = 2.0**56                  # offsets up to 2^28 pixels: the int conversion and x + offset fit
+
 
 class FrameParams(ctypes.Structure):
     _fields_ = [

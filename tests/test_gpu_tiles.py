@@ -32,6 +32,9 @@ def _emulate(sc, W, H, prm, n_ranks, cams, margin):
             for p in range(prm.spatial_passes):
                 torch.cuda.synchronize()
                 for r, be in enumerate(bes):
+                    if h == 0:                      # a radius below 1: no neighbour leaves its pixel, no halo rows
+                        assert all(be.halo_tensor(i) is None for i in range(4))
+                        continue
                     if r > 0:
                         be.halo_tensor(0).copy_(bes[r - 1].halo_tensor(3))
                     if r < n_ranks - 1:

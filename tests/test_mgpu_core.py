@@ -116,6 +116,17 @@ def test_native_band_balancing_matches_python():
             assert [(int(out[i]), int(out[i + 1])) for i in range(world)] == py, (H, world, mr)
     for r in (30.0, 24.999998, 24.9, 25.0, 0.5, 0.0):
         assert L.harness_halo(r) == halo_rows(P.metric_params(spatial_radius=r))
+    # the ends of the domain [0, 2^56] and the halos of tests/param_cases.py
+    for r, want in ((-0.0, 0), (0.99, 0), (1.0, 1), (150.0, 12), (400.0, 20), (1.0e6, 1000),
+                    (P.MAX_SPATIAL_RADIUS, 2**28)):
+        assert L.harness_halo(r) == halo_rows(P.metric_params(spatial_radius=r)) == want, r
+    # outside it both refuse: -1 here, ValueError there -- never a halo of 0 rows, never an enormous one
+    above = float(np.nextafter(np.float32(P.MAX_SPATIAL_RADIUS), np.float32(np.inf)))
+    for r in (-1.0, -1e-30, float("nan"), float("inf"), float("-inf"), 1e20, above):
+        assert L.harness_halo(r) == -1, r
+        with pytest.raises(ValueError):
+            halo_rows(P.metric_params(spatial_radius=r))
+        assert halo_rows(P.default_params(spatial_radius=r)) == 0       # no spatial pass: no halo, whatever the radius
 
 
 def test_band_balancing_on_wave_tiles():
