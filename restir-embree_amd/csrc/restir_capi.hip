@@ -13,6 +13,7 @@
 #include "rs_image.h"
 #include "rs_internal.h"
 #include "rs_frame_ring.h"
+#include "rs_build.h"
 
 #include <cmath>
 #include <cstdio>
@@ -22,18 +23,6 @@
 #include <vector>
 #include <algorithm>
 #include <type_traits>
-
-namespace rs {
-int build_bvh(const float* d_pos, uint32_t n, hipStream_t st, float4** d_nodes, uint32_t* n_nodes, float4** d_tris,
-              WideBvh* wide, std::string& err);
-void preload_code_objects();
-void builder_pool_trim();
-int bvh_refit_plan(const float4* d_nodes, uint32_t n_nodes, hipStream_t st, int** d_order, int** d_lvl_off,
-                   std::vector<int>& lvl_off, std::string& err);
-int bvh_refit(float4* d_nodes, float4* d_tris, const float* d_pos, const int* d_order, const int* d_lvl_off,
-              const std::vector<int>& lvl_off, hipStream_t st, int* tail, std::string& err);
-void wide_free(WideBvh& w);
-}
 
 using namespace rs;
 

@@ -1,18 +1,24 @@
-// rs_bvh_build.hip -- wavefront LBVH build on the GPU; replaces Embree's rtcCommitScene
-// (pg/Scene.cpp:15).  Every stage is a data-parallel kernel; no inter-workgroup hand-off inside a
-// launch (kernel boundaries provide visibility across the 8 non-coherent XCD L2s), so the build is
-// placement-independent and deterministic (identical trees on every rank):
-//   1 k_prim_bounds   per-triangle AABB + centroid; centroid bounds by block reduce + ordered-int
-//                     atomics (min/max are order independent)
-//   2 k_morton        64-bit key = morton30(centroid) << 32 | triangle index (unique keys)
-//   3 radix sort      hipcub::DeviceRadixSort::SortKeys on 62 bits
-//   4 k_karras        Karras 2012 hierarchy: internal node i's range, split, children, parents
-//   5 k_depth         depth of every node (walk to the root)
-//   6 k_refit_level   bottom-up AABB union + collapsed subtree sizes, one launch per depth level
-//   7 k_emit          collapse subtrees of <= kLeafMax triangles into leaves, preorder index by
+// rs_bvh_build.hip -- the binary skip-pointer tree, built on the GPU; replaces, with the 8-wide tree of
+// rs_wide_build.hip, Embree's rtcCommitScene (pg/Scene.cpp:15).  Every stage is a data-parallel kernel; no
+// inter-workgroup hand-off inside a launch (kernel boundaries provide visibility across the 8 non-coherent XCD L2s),
+// so a build is placement-independent and deterministic (identical trees on every rank).  The file holds, in order:
+//   the Morton front end that both builders run:
+//     k_prim_bounds   per-triangle AABB + centroid; centroid bounds by block reduce + ordered-int atomics
+//                     (min/max are order independent)
+//     k_morton        64-bit key = morton30(centroid) << 32 | triangle index (unique keys)
+//     radix sort      hipcub::DeviceRadixSort::SortKeys on 62 bits
+//   the LBVH, kept for comparison (RESTIR_BVH=lbvh; build_bvh_lbvh):
+//     k_karras        Karras 2012 hierarchy: internal node i's range, split, children, parents
+//     k_depth         depth of every node (walk to the root)
+//     k_refit_level   bottom-up AABB union + collapsed subtree sizes, one launch per depth level
+//     k_emit          collapse subtrees of <= kLeafMax triangles into leaves, preorder index by
 //                     walking up (idx = idx(parent) + 1 + [right child] * kept(left sibling)),
 //                     write the 32-B skip-pointer nodes
-//   8 k_leaf_tris     triangles in leaf order as (v0, prim), (e1), (e2)
+//     k_leaf_tris     triangles in leaf order (rs_refit.h write_tri)
+//   PLOC, the default builder (build_bvh_ploc; its kernels are introduced below)
+//   the builder pool that serves PLOC's and the wide builder's scratch
+//   the launches of the in-place refit (rs_refit.h) and its plan
+//   builder selection (build_bvh) and the code-object preload
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -25,19 +31,13 @@
 #include <cstring>
 #include <algorithm>
 #include <mutex>
-#include "rs_refit.h"
+#include "rs_build.h"
 #include "rs_wide.h"
 #include "../../include/restir_c.h"
 
 namespace rs {
 
 constexpr int kLeafMax = 4;
-
-__device__ __forceinline__ int f2o(float f) {   // order-preserving float -> int
-    int i = __float_as_int(f);
-    return i >= 0 ? i : i ^ 0x7fffffff;
-}
-__device__ __forceinline__ float o2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 
 struct BuildNode {        // internal nodes [0, n-1), leaves [n-1, 2n-1)
     float lo[3], hi[3];
@@ -206,12 +206,7 @@ __global__ void k_emit(const BuildNode* N, int n, float4* out) {
 __global__ void k_leaf_tris(const float* __restrict__ pos, const uint64_t* keys, uint32_t n, float4* tris) {
     uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
-    uint32_t prim = (uint32_t)(keys[k] & 0xffffffffu);
-    const float* p = pos + 9 * (size_t)prim;
-    float v0x = p[0], v0y = p[1], v0z = p[2];
-    tris[3 * k] = make_float4(v0x, v0y, v0z, __int_as_float((int)prim));
-    tris[3 * k + 1] = make_float4(p[3] - v0x, p[4] - v0y, p[5] - v0z, 0.0f);
-    tris[3 * k + 2] = make_float4(p[6] - v0x, p[7] - v0y, p[8] - v0z, 0.0f);
+    write_tri(tris, k, pos, (uint32_t)(keys[k] & 0xffffffffu));
 }
 
 #define BVH_CHECK(x)                                                                   \
@@ -472,14 +467,7 @@ __global__ void k_ploc_emit(const float4* nlo, const float4* nhi, const int* par
         idx += 1;
         if (L != ch) { idx += kept[L]; off += cnt[L]; }   // ch is the right child
     }
-    if (c < n) {   // primitive: its triangle slot is `off`
-        int prim = __float_as_int(nhi[c].w);
-        const float* p = pos + 9 * (size_t)prim;
-        float v0x = p[0], v0y = p[1], v0z = p[2];
-        tris[3 * off] = make_float4(v0x, v0y, v0z, __int_as_float(prim));
-        tris[3 * off + 1] = make_float4(p[3] - v0x, p[4] - v0y, p[5] - v0z, 0.0f);
-        tris[3 * off + 2] = make_float4(p[6] - v0x, p[7] - v0y, p[8] - v0z, 0.0f);
-    }
+    if (c < n) write_tri(tris, off, pos, __float_as_int(nhi[c].w));   // primitive: its triangle slot is `off`
     if (!emitted) return;
     bool leaf = (c < n) || collapsed[c];
     int skip = idx + (leaf ? 1 : kept[c]);
@@ -637,7 +625,7 @@ int build_bvh_ploc(const float* d_pos, uint32_t n, hipStream_t st, float4** d_no
     nodes = nullptr; tris = nullptr;
 fail: {
         // scratch: stream-ordered frees into the device pool (no synchronisation; the next build's or the wide
-        // build's allocations reuse it, see build_pool_setup); the outputs are ordinary allocations
+        // build's allocations reuse it, see builder_pool above); the outputs are ordinary allocations
         void* ptrs[] = {lo, hi, nlo, nhi, cb, cnt, parent, C0, C1, N, valid, merged, pos, mid, depth,
                         dmax, kept, collapsed, cost, keys, keys_sorted, tmp, tmp2, pst};
         for (void* p : ptrs) if (p) (void)hipFreeAsync(p, st);
@@ -702,12 +690,6 @@ int bvh_refit(float4* d_nodes, float4* d_tris, const float* d_pos, const int* d_
     return 0;
 }
 
-// builder selection: PLOC by default; RESTIR_BVH=lbvh selects the Karras LBVH (kept for comparison).  Then the
-// 8-wide tree of the per-lane walks from the positions alone (rs_wide_build.hip); it is optional: when it does
-// not apply (non-finite positions, no plan within the walk's depth) or its build fails, the scene keeps the
-// binary tree and the walks take the skip pointers (RESTIR_WIDE=off: never built).
-int build_wide_gpu(const float* d_pos, int n, hipStream_t st, WideBvh* w, std::string& err);
-void preload_wide_build();
 // HIP loads a source file's code object at the first launch (or attribute query) of one of its kernels: at
 // context creation, so that a scene build is not charged the one-time load of the builders (~10 ms at C3)
 void preload_code_objects() {
@@ -722,6 +704,10 @@ void wide_free(WideBvh& w) {
     for (void* q : p) if (q) hipFree(q);
     w = WideBvh{};
 }
+// builder selection: PLOC by default; RESTIR_BVH=lbvh selects the Karras LBVH (kept for comparison).  Then the
+// 8-wide tree of the per-lane walks from the positions alone (rs_wide_build.hip); it is optional: when it does
+// not apply (non-finite positions, no plan within the walk's depth) or its build fails, the scene keeps the
+// binary tree and the walks take the skip pointers (RESTIR_WIDE=off: never built).
 int build_bvh(const float* d_pos, uint32_t n, hipStream_t st, float4** d_nodes, uint32_t* n_nodes, float4** d_tris,
               WideBvh* wide, std::string& err) {
     const char* e = getenv("RESTIR_BVH");

@@ -3,9 +3,9 @@
 //
 // The topology stays; every node's box is recomputed from the new vertex positions exactly as the
 // builders compute it (per-triangle min/max of the three vertices, unions by fminf/fmaxf -- order
-// independent), and the leaf triangles are rewritten from the new positions with the same operations
-// as k_ploc_emit.  Since the box test is conservative and the closest-hit tie rule does not depend on
-// visit order, a refit tree answers every query bit-identically to a freshly built one
+// independent), and the leaf triangles are rewritten from the new positions by the builders' own
+// writer (write_tri below).  Since the box test is conservative and the closest-hit tie rule does not
+// depend on visit order, a refit tree answers every query bit-identically to a freshly built one
 // (tests/test_gpu_parity.py::test_update_positions_refit_matches_fresh_scene).
 //
 // Nodes are processed deepest level first; an interior node's children (i + 1 and the left child's
@@ -51,6 +51,19 @@ struct WideBvh {
 constexpr int kRefitBlock = RS_REFIT_BLOCK;
 constexpr int kRefitSmall = 4096;                // levels up to this many nodes go to the 1-block batch
 
+// The leaf-triangle record of both trees, as the walks read it (rs_scene.h tri_test): record k of `tris` is
+// (v0, prim), (e1 = v1 - v0), (e2 = v2 - v0) of triangle `prim` at pos (9 floats each).  Builders and refits all
+// write it here, with these very subtractions, so a refit tree's triangles equal a fresh build's bit for bit.
+// (Index, Prim: the caller's own integer types, so that 3 * k and 9 * prim are formed as they were at each site.)
+template <class Index, class Prim>
+__device__ __forceinline__ void write_tri(float4* tris, Index k, const float* pos, Prim prim) {
+    const float* p = pos + 9 * (size_t)prim;
+    const float v0x = p[0], v0y = p[1], v0z = p[2];
+    tris[3 * k] = make_float4(v0x, v0y, v0z, __int_as_float((int)prim));
+    tris[3 * k + 1] = make_float4(p[3] - v0x, p[4] - v0y, p[5] - v0z, 0.0f);
+    tris[3 * k + 2] = make_float4(p[6] - v0x, p[7] - v0y, p[8] - v0z, 0.0f);
+}
+
 __device__ __forceinline__ void refit_node(float4* nodes, float4* tris, const float* __restrict__ pos, int i) {
     const float4 a = nodes[2 * i], b = nodes[2 * i + 1];
     const int leaf = __float_as_int(b.w);
@@ -66,10 +79,7 @@ __device__ __forceinline__ void refit_node(float4* nodes, float4* tris, const fl
                 l[ax] = fminf(l[ax], fminf(fminf(p[ax], p[3 + ax]), p[6 + ax]));
                 h[ax] = fmaxf(h[ax], fmaxf(fmaxf(p[ax], p[3 + ax]), p[6 + ax]));
             }
-            const float v0x = p[0], v0y = p[1], v0z = p[2];
-            tris[3 * k] = make_float4(v0x, v0y, v0z, __int_as_float(prim));
-            tris[3 * k + 1] = make_float4(p[3] - v0x, p[4] - v0y, p[5] - v0z, 0.0f);
-            tris[3 * k + 2] = make_float4(p[6] - v0x, p[7] - v0y, p[8] - v0z, 0.0f);
+            write_tri(tris, k, pos, prim);
         }
     } else {
         const int L = i + 1, R = __float_as_int(nodes[2 * L].w);
@@ -145,10 +155,7 @@ __device__ __forceinline__ void wide_refit_node(const WideRefitArgs& A, uint32_t
             // stays encodable and its planes stay a superset of the finite triangles below
             if (!fin)
                 for (int a = 0; a < 3; ++a) kb[i].lo[a] = kb[i].hi[a] = 0.0f;
-            const float v0x = p[0], v0y = p[1], v0z = p[2];
-            A.tris[3 * t] = make_float4(v0x, v0y, v0z, __int_as_float(prim));
-            A.tris[3 * t + 1] = make_float4(p[3] - v0x, p[4] - v0y, p[5] - v0z, 0.0f);
-            A.tris[3 * t + 2] = make_float4(p[6] - v0x, p[7] - v0y, p[8] - v0z, 0.0f);
+            write_tri(A.tris, t, A.pos, prim);
         }
     }
     uint32_t w[20];

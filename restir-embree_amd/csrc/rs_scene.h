@@ -38,7 +38,7 @@ struct DevScene {
     const uint8_t* tex;       // texel bytes of every texture
     const int4* texd;         // 2 per texture: (byte offset, width, height, pitch), (pixel bytes, format, 0, 0)
     int sky;                  // texture index of the equirect sky, -1 none
-    // 8-wide tree of the per-lane walks (rs_bvh_build.hip build_wide); n_wnodes = 0: skip-pointer walks
+    // 8-wide tree of the per-lane walks (rs_wide_build.hip build_wide_gpu); n_wnodes = 0: skip-pointer walks
     const uint4* wnodes;      // 5 per node
     const float4* wtris;      // 3 per wide-leaf triangle: (v0, prim) (e1) (e2)
     uint32_t n_wnodes;
@@ -244,7 +244,7 @@ __device__ __forceinline__ void closest_lane_from(const DevScene& S, uint32_t i,
 // ---------------------------------------------------------------- 8-wide per-lane walks (TRAV_LANE)
 // The skip-pointer walk fetches every child of every entered node to test that child's box: ~75 dependent
 // 32-B node loads per C3 shadow ray, and the per-lane walks are bound by those lane-loads and the VALU of
-// one box test per step.  The 8-wide tree (rs_bvh_build.hip build_wide: 80-B nodes
+// one box test per step.  The 8-wide tree (rs_wide_build.hip build_wide_gpu: 80-B nodes
 // holding the quantised boxes of up to 8 children) tests all children of a node per fetch: ~14 node
 // fetches per shadow ray (5 x 16-B loads each), i.e. about half the lane-loads, a fifth of the
 // dependent-load chain, and 8 box tests per fetch that share the node's per-axis setup.

@@ -22,7 +22,7 @@
 //   5 k_wide_kids / k_wide_emit   the wide nodes breadth-first, one launch pair per wide level (<= 9): each
 //                     node expands its slots from the tables, exclusive scans place its interior children and
 //                     leaf triangles, and rs_wide.h wide_encode quantises its child boxes (outward, exact)
-//   6 k_wide_gather   the wide-leaf triangles (v0, prim) (e1) (e2)
+//   6 k_wide_gather   the wide-leaf triangles (rs_refit.h write_tri)
 // Every choice is a function of a node's triangle set, so the arrays' order inside a level never matters.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -31,11 +31,9 @@
 #include <string>
 #include <vector>
 #include <algorithm>
-#include "rs_refit.h"
+#include "rs_build.h"
 #include "../../include/restir_c.h"
 #include "rs_wide.h"
-
-namespace rs { hipError_t pool_malloc(void** p, size_t bytes, hipStream_t st); }
 
 namespace rs {
 namespace wb {
@@ -49,8 +47,6 @@ constexpr float kCnode = 1.0f, kCtri = 0.3f;   // build_wide_host's defaults
 constexpr int kG = SahCollapse::kG; // g = -1 .. 8
 constexpr int kGmax = RS_WIDE_STACK;
 
-__device__ __forceinline__ int f2o(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
-__device__ __forceinline__ float o2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 __device__ __forceinline__ double half_area_d(const float* lo, const float* hi) {   // build_sah_host half_area
     const double x = (double)hi[0] - lo[0], y = (double)hi[1] - lo[1], z = (double)hi[2] - lo[2];
     return x * y + y * z + z * x;
@@ -824,16 +820,11 @@ __global__ void k_level_totals(const int* si, const int* ni, const int* sl, cons
 __global__ void k_wide_gather(const float* __restrict__ pos, const int* __restrict__ prims, uint32_t m, float4* tris) {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= m) return;
-    const int prim = prims[k];
-    const float* p = pos + 9 * (size_t)prim;
-    const float v0x = p[0], v0y = p[1], v0z = p[2];
-    tris[3 * k] = make_float4(v0x, v0y, v0z, __int_as_float(prim));
-    tris[3 * k + 1] = make_float4(p[3] - v0x, p[4] - v0y, p[5] - v0z, 0.0f);
-    tris[3 * k + 2] = make_float4(p[6] - v0x, p[7] - v0y, p[8] - v0z, 0.0f);
+    write_tri(tris, k, pos, prims[k]);
 }
 
-// device scratch freed on every exit
-// stream-ordered scratch from the device pool (rs_bvh_build.hip preload_code_objects keeps it cached)
+// device scratch: stream-ordered allocations from the builders' pool (rs_bvh_build.hip pool_malloc), freed with
+// hipFreeAsync on every exit
 struct Scratch {
     hipStream_t st;
     std::vector<void*> p;
@@ -855,9 +846,6 @@ struct Scratch {
     } while (0)
 #define WB_HIP(x) WB_CHECK((x) == hipSuccess, #x)
 
-// Builds the 8-wide tree of the n triangles at d_pos (device, 9 floats each) on `st`.  Returns 0 with *w filled
-// (device allocations owned by the caller), 1 when no tree applies (non-finite positions, or no plan within the
-// walk's depth: the walks then take the skip pointers; *w stays empty), -1 on a HIP error (err set).
 // the code object of this file loaded now (HIP loads a file's kernels at its first launch or query; see
 // rs::preload_code_objects)
 void preload_wide_build() {
@@ -865,6 +853,9 @@ void preload_wide_build() {
     (void)hipFuncGetAttributes(&fa, (const void*)wb::k_small);
 }
 
+// Builds the 8-wide tree of the n triangles at d_pos (device, 9 floats each) on `st`.  Returns 0 with *w filled
+// (device allocations owned by the caller), 1 when no tree applies (non-finite positions, or no plan within the
+// walk's depth: the walks then take the skip pointers; *w stays empty), -1 on a HIP error (err set).
 int build_wide_gpu(const float* d_pos, int n, hipStream_t st, WideBvh* w, std::string& err) {
     using namespace wb;
     *w = WideBvh{};
