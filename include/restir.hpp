@@ -88,6 +88,13 @@ public:
         replace_scene(s);
     }
 
+    // Raytracer::LoadScene's skybox (Scene::loadSkybox): an equirect .hdr / .pfm / .ppm / .png for params.use_skybox
+    void LoadSky(const std::string& path) {
+        if (!scene_) throw Error(RS_E_INVALID, "LoadSky: no scene loaded");
+        finish();
+        check(rs_scene_load_sky(scene_, path.c_str()), ctx_);
+    }
+
     // SimpleGuiDX11::produceRestir(t): one frame with the current camera_ and params; frame_data()
     // then holds the linear-HDR framebuffer, the duration members the per-pass device times.
     //   pipelineDepth = 0 (reference semantics): frame_data() is this frame (the call waits for it).
@@ -127,12 +134,15 @@ public:
     // totalFrameDuration the launch.  The ReSTIR history is untouched; frameCtr keys the RNG and advances.
     // unbiasedEstimator: rs_render_path_unbiased instead -- the textbook NEE + MIS estimator, which equals the
     // light where the reference's is dark (materials with Kd and Ks); params.normal_offset is not used by it.
+    // skyLight (with unbiasedEstimator): rs_render_path_sky -- the same with the environment as a light, sampled from
+    // tables of the sky's texels and counted at every vertex.
     void produceStandard(float t = 0.0f) {
         (void)t;
         if (!scene_) throw Error(RS_E_INVALID, "produceStandard: no scene loaded");
         finish();
         rs_pass_times pt{};
-        check((unbiasedEstimator ? rs_render_path_unbiased : rs_render_path)(
+        if (skyLight && !unbiasedEstimator) throw Error(RS_E_INVALID, "produceStandard: skyLight needs unbiasedEstimator");
+        check((skyLight ? rs_render_path_sky : unbiasedEstimator ? rs_render_path_unbiased : rs_render_path)(
                   ctx_, scene_, &camera_, &params, &pathParams, frameCtr, samplesPerPixel, ring_[cur_],
                   timePasses ? &pt : nullptr), ctx_);
         shown_ = ring_[cur_]; shown_frame_ = (long long)frameCtr;
@@ -190,6 +200,7 @@ public:
     rs_path_params pathParams{5, 1, 1, 1};
     uint32_t samplesPerPixel = 1;
     bool unbiasedEstimator{false};          // produceStandard: the unbiased estimator instead of the reference's
+    bool skyLight{false};                   // ... and with it the environment as a light (rs_render_path_sky)
     uint32_t frameCtr = 0;
     int pipelineDepth = 0;
     bool timePasses = true;
@@ -266,8 +277,10 @@ public:
     void produceStandard(float t = 0.0f) {
         (void)t;
         const std::vector<const rs_scene*> scenes = group();
+        if (skyLight && !unbiasedEstimator) throw Error(RS_E_INVALID, "produceStandard: skyLight needs unbiasedEstimator");
         check(rs_mgpu_render_ground_truth(m_, scenes.data(), &camera_, &params,
-                                          unbiasedEstimator ? RS_GT_PATH_UNBIASED : RS_GT_PATH, &pathParams, frameCtr,
+                                          skyLight ? RS_GT_PATH_UNBIASED_SKY
+                                                   : unbiasedEstimator ? RS_GT_PATH_UNBIASED : RS_GT_PATH, &pathParams, frameCtr,
                                           samplesPerPixel, 1, frame_.data(), nullptr), ranks_[0]->handle());
         ++frameCtr;
     }
@@ -289,6 +302,7 @@ public:
     rs_path_params pathParams{5, 1, 1, 1};
     uint32_t samplesPerPixel = 1;
     bool unbiasedEstimator{false};
+    bool skyLight{false};
     uint32_t frameCtr = 0;
 
 private:

@@ -269,13 +269,29 @@ int rs_render_path(rs_context* ctx, const rs_scene* scene, const rs_camera* came
 int rs_render_path_unbiased(rs_context* ctx, const rs_scene* scene, const rs_camera* camera,
                             const rs_frame_params* params, const rs_path_params* path, uint32_t frame_index,
                             uint32_t spp, float* frame_rgb_host, rs_pass_times* times);
+/* ---- The same with the environment as a light: the ground truth under a sky ----------------------- */
+/* rs_render_path_unbiased counts the environment (the sky with use_skybox, else bg_color) only where the BRDF ray
+ * of a vertex that is not the path's last one misses: with calc_gi = 0 a surface under the sky is black, with
+ * max_bounces = m the environment's light on vertex m is missing, and a sun in the sky is found only by chance.
+ * This entry counts the environment at every vertex and samples the sky: a direction from a vertex ends on an
+ * emitter, on another surface or in the environment; the emitters keep their two strategies and the environment
+ * gets its own two -- one sky sample per vertex, drawn from integer sampling tables of the sky's texels (built on
+ * the device on the first such render after a sky is set, kept on the scene until the sky changes) with an any-hit
+ * ray from the surface point, and the BRDF ray where it misses, at the last vertex too -- joined by the power
+ * heuristic.  With use_skybox = 0, or under a sky without light, the environment is sampled by the BRDF ray alone;
+ * with calc_di = 0 the environment counts nothing, as emitters do.  A primary miss shows the sky or bg_color, as
+ * everywhere.  Signature, contract, error codes and ranges of rs_render_path_unbiased; also RS_E_UNSUPPORTED:
+ * use_skybox with a sky wider than 32768 texels. */
+int rs_render_path_sky(rs_context* ctx, const rs_scene* scene, const rs_camera* camera,
+                       const rs_frame_params* params, const rs_path_params* path, uint32_t frame_index,
+                       uint32_t spp, float* frame_rgb_host, rs_pass_times* times);
 /* ---- A ground truth over a row set: the single-context piece of a multi-GPU ground truth ------------- */
 /* The rows y in [0, H) with (y / strip_rows) % stride == phase: strips of strip_rows rows (a positive multiple
  * of RS_ROW_STRIP, the height of a workgroup's pixel tile) dealt out round robin to `stride` owners, this one
  * being owner `phase`.  A ground-truth pixel is independent of every other and its random stream is keyed by
  * the full-frame pixel index, so the strips of all phases assemble the full-frame entry's frame bit for bit;
  * {RS_ROW_STRIP, 1, 0} is that entry.  estimator picks rs_render_direct_mis (path = NULL), rs_render_path or
- * rs_render_path_unbiased, whose contract, error codes and ranges hold: one launch on the context's stream,
+ * rs_render_path_unbiased or rs_render_path_sky, whose contract, error codes and ranges hold: one launch on the context's stream,
  * ReSTIR history untouched.  Only the rows of the set are written, every other row of the framebuffer keeps its
  * contents (frame_rgb_host receives the whole framebuffer); times->rays and primary_rays count this launch
  * only.  A set with no row in [0, H) launches nothing and returns RS_OK with zero rays.  Also RS_E_INVALID:
@@ -288,6 +304,7 @@ typedef struct { int32_t strip_rows, stride, phase; } rs_row_set;
 #define RS_GT_DIRECT_MIS 0
 #define RS_GT_PATH 1
 #define RS_GT_PATH_UNBIASED 2
+#define RS_GT_PATH_UNBIASED_SKY 4     /* 3 is not an estimator: it stays RS_E_INVALID, as callers have been promised */
 int rs_render_ground_truth_rows(rs_context* ctx, const rs_scene* scene, const rs_camera* camera,
                                 const rs_frame_params* params, int estimator, const rs_path_params* path,
                                 uint32_t frame_index, uint32_t spp, const rs_row_set* rows,
@@ -617,6 +634,12 @@ int rs_debug_bvh_tree(const rs_scene* scene, uint32_t* n_nodes, uint32_t* n_tris
  * cdf != NULL (*n_emis floats) the light CDF and with guide != NULL (1025 int32) its guide table, guide[j] =
  * lower_bound(cdf, j / 1024).  It waits for a pipelined rs_scene_update_positions and synchronises. */
 int rs_debug_light_tables(const rs_scene* scene, uint32_t* n_emis, float* em, float* cdf, int32_t* guide);
+/* Test hook: the sampling tables of the scene's sky (rs_render_path_sky), built if the scene has none yet.  *w, *h:
+ * the sky's size in texels; row_cdf: h rows of w uint32, per row the inclusive prefix sum of the cells' integer
+ * weights q(i, j); marginal: h uint64, the inclusive prefix sum of the row totals.  With row_cdf and marginal both
+ * NULL only the size is returned and nothing is built.  Synchronises.  RS_E_INVALID: null scene, w or h, a tile
+ * frame in flight; RS_E_UNSUPPORTED: no sky, or one wider than 32768 texels. */
+int rs_debug_sky_tables(const rs_scene* scene, uint32_t* w, uint32_t* h, uint32_t* row_cdf, uint64_t* marginal);
 
 #ifdef __cplusplus
 }

@@ -79,6 +79,17 @@ struct rs_scene {
     uint8_t* d_tex = nullptr;
     int4* d_texd = nullptr;
     float4 *d_uv = nullptr, *d_tan = nullptr;
+    // the sky's sampling tables (rs_sky.h): built on the first sky-light render after a sky is set (ensure_sky_tables),
+    // dropped when the sky changes; callers that never ask for that estimator allocate nothing
+    mutable uint32_t* d_sky_cdf = nullptr;
+    mutable uint64_t* d_sky_marg = nullptr;
+    mutable uint64_t sky_total = 0;
+    mutable bool sky_tables = false;
+    void drop_sky_tables() const {
+        if (d_sky_cdf) hipFree(d_sky_cdf);
+        if (d_sky_marg) hipFree(d_sky_marg);
+        d_sky_cdf = nullptr; d_sky_marg = nullptr; sky_total = 0; sky_tables = false;
+    }
     // per-scene traversal choice (RS_TRAVERSAL_AUTO): frame times of each kind, tuning frames counted
     mutable int trav_choice = -1;
     mutable int trav_runs[2] = {0, 0};
@@ -1181,6 +1192,7 @@ extern "C" int rs_scene_set_sky(rs_scene* s, const rs_texture_desc* d) {
     rs_scene::HostTex t;
     std::string err;
     if (d && !prepare_texture(*d, 0, t, err)) return fail(c, RS_E_INVALID, "rs_scene_set_sky: " + err);
+    s->drop_sky_tables();
     if (s->sky >= 0) { s->h_tex.pop_back(); s->sky = -1; }
     if (d) { s->h_tex.push_back(std::move(t)); s->sky = (int)s->h_tex.size() - 1; }
     if (upload_textures(c, s, err) != 0) return fail(c, RS_E_HIP, "rs_scene_set_sky: " + err);
@@ -1221,6 +1233,7 @@ extern "C" void rs_scene_destroy(rs_scene* s) {
     void* ptrs[] = {s->d_pos, s->d_tri_nrm, s->d_mats, s->d_emis_tri, s->d_refit_order, s->d_refit_lvl, s->d_nrm_stage,
                     s->d_tex, s->d_texd, s->d_uv, s->d_tan, s->a_tri_nrm, s->d_ebucket};
     for (void* p : ptrs) if (p) hipFree(p);
+    s->drop_sky_tables();
     geo_free(s->geo);
     geo_free(s->alt);
     for (int k = 0; k < 2; ++k) {
@@ -2083,7 +2096,8 @@ extern "C" int rs_render_direct_mis(rs_context* c, const rs_scene* s, const rs_c
 template <class Kernel>
 static int render_path_with(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
                             const rs_path_params* pp, uint32_t frame_index, uint32_t spp, const rs_row_set* rows,
-                            float* frame_rgb_host, rs_pass_times* t, const char* who, Kernel&& kernel) {
+                            float* frame_rgb_host, rs_pass_times* t, const char* who, Kernel&& kernel,
+                            const SkyLight K = SkyLight{}) {
     const std::string fn = who;
     if (!pp) return fail(c, RS_E_INVALID, fn + ": null argument");
     if (pp->max_bounces < 0 || pp->max_bounces > 15)
@@ -2098,7 +2112,7 @@ static int render_path_with(rs_context* c, const rs_scene* s, const rs_camera* c
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) return e;
         }
-        k<<<g, kPathBlock, lds, c->fr.fs>>>(S, F, Q, c->lane().fb, slot, R);
+        k<<<g, kPathBlock, lds, c->fr.fs>>>(S, F, Q, c->lane().fb, slot, R, K);
         return hipGetLastError();
     });
 }
@@ -2119,7 +2133,71 @@ extern "C" int rs_render_path_unbiased(rs_context* c, const rs_scene* s, const r
                             [](auto T, auto R) { return &k_path<T(), kEstUnbiased, R()>; });
 }
 
-// Any of the three over a row set (restir_c.h): the same launch, the set's strips only
+// The scene's sky tables for a sky-light render (rs_sky.h), built on the context's stream if the scene has none yet.
+// Without use_skybox the estimator samples no sky and nothing is built.  The checks that decide whether the render
+// will run at all come first, in render_ground_truth's order, so that a call it refuses builds nothing.
+static int ensure_sky_tables(rs_context* c, const rs_scene* s, std::string& err, int& code) {
+    code = RS_E_HIP;
+    if (s->sky_tables) return 0;
+    const rs_scene::HostTex& t = s->h_tex[(size_t)s->sky];
+    if (t.w > kSkyMaxWidth) {
+        code = RS_E_UNSUPPORTED;
+        err = "the sky is wider than 32768 texels: its rows' sampling tables would not fit 32 bits";
+        return -1;
+    }
+    if (build_sky_tables(s->dev(), t.w, t.h, c->stream, &s->d_sky_cdf, &s->d_sky_marg, &s->sky_total, err) != 0) return -1;
+    s->sky_tables = true;
+    return 0;
+}
+
+// The unbiased NEE + MIS path tracer with the environment as a light (rs_path.h, kEstUnbiasedSky)
+static int render_path_sky_with(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                                const rs_path_params* pp, uint32_t frame_index, uint32_t spp, const rs_row_set* rows,
+                                float* frame_rgb_host, rs_pass_times* t, const char* who) {
+    SkyLight K{};
+    // what render_path_with and render_ground_truth refuse is refused there, with their messages, before anything
+    // is built: the tables are made only for a call that passes these
+    const bool sound = c && s && cam && P && pp && s->ctx == c && !c->fr.active && spp >= 1 && spp <= 65536 &&
+                       pp->max_bounces >= 0 && pp->max_bounces <= 15;
+    if (sound && P->use_skybox && s->sky >= 0) {
+        HIPCHK(c, enter(c));
+        std::string err;
+        int code;
+        if (ensure_sky_tables(c, s, err, code) != 0) return fail(c, code, std::string(who) + ": " + err);
+        K = SkyLight{s->d_sky_cdf, s->d_sky_marg, s->h_tex[(size_t)s->sky].w, s->h_tex[(size_t)s->sky].h, s->sky_total};
+    }
+    return render_path_with(c, s, cam, P, pp, frame_index, spp, rows, frame_rgb_host, t, who,
+                            [](auto T, auto R) { return &k_path<T(), kEstUnbiasedSky, R()>; }, K);
+}
+
+extern "C" int rs_render_path_sky(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
+                                  const rs_path_params* pp, uint32_t frame_index, uint32_t spp, float* frame_rgb_host,
+                                  rs_pass_times* t) {
+    return render_path_sky_with(c, s, cam, P, pp, frame_index, spp, nullptr, frame_rgb_host, t, "rs_render_path_sky");
+}
+
+// Test hook: the scene's sky tables, built if needed (restir_c.h)
+extern "C" int rs_debug_sky_tables(const rs_scene* s, uint32_t* w, uint32_t* h, uint32_t* row_cdf, uint64_t* marginal) {
+    if (!s || !w || !h) return fail(s ? s->ctx : nullptr, RS_E_INVALID, "rs_debug_sky_tables: null argument");
+    rs_context* c = s->ctx;
+    if (c->fr.active) return fail(c, RS_E_INVALID, "rs_debug_sky_tables: a tile frame is in flight");
+    if (s->sky < 0) return fail(c, RS_E_UNSUPPORTED, "rs_debug_sky_tables: the scene has no sky map");
+    HIPCHK(c, enter(c));
+    const rs_scene::HostTex& t = s->h_tex[(size_t)s->sky];
+    *w = (uint32_t)t.w; *h = (uint32_t)t.h;
+    if (!row_cdf && !marginal) return RS_OK;
+    std::string err;
+    int code;
+    if (ensure_sky_tables(c, s, err, code) != 0) return fail(c, code, "rs_debug_sky_tables: " + err);
+    if (row_cdf)
+        HIPCHK(c, hipMemcpyAsync(row_cdf, s->d_sky_cdf, (size_t)t.w * t.h * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (marginal)
+        HIPCHK(c, hipMemcpyAsync(marginal, s->d_sky_marg, (size_t)t.h * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RS_OK;
+}
+
+// Any of the four over a row set (restir_c.h): the same launch, the set's strips only
 extern "C" int rs_render_ground_truth_rows(rs_context* c, const rs_scene* s, const rs_camera* cam, const rs_frame_params* P,
                                            int estimator, const rs_path_params* pp, uint32_t frame_index, uint32_t spp,
                                            const rs_row_set* rows, float* frame_rgb_host, rs_pass_times* t) {
@@ -2134,6 +2212,8 @@ extern "C" int rs_render_ground_truth_rows(rs_context* c, const rs_scene* s, con
     case RS_GT_PATH_UNBIASED:
         return render_path_with(c, s, cam, P, pp, frame_index, spp, rows, frame_rgb_host, t, who,
                                 [](auto T, auto R) { return &k_path<T(), kEstUnbiased, R()>; });
+    case RS_GT_PATH_UNBIASED_SKY:
+        return render_path_sky_with(c, s, cam, P, pp, frame_index, spp, rows, frame_rgb_host, t, who);
     }
     return fail(c, RS_E_INVALID, std::string(who) + ": unknown estimator");
 }

@@ -20,7 +20,8 @@ namespace rs {
 constexpr uint32_t kPassMis = 64u;
 // the estimators of the ground truths: the reference's, restated bit for bit with its three biases, and
 // the textbook NEE + MIS one over the same material model (rs_path.h)
-constexpr int kEstReference = 0, kEstUnbiased = 1;
+// kEstUnbiasedSky: the unbiased one with the environment as a light (rs_path.h, rs_sky.h)
+constexpr int kEstReference = 0, kEstUnbiased = 1, kEstUnbiasedSky = 2;
 
 struct MisSurf { vec3 pos, n, wr, kd, ks; float shin, i_m, maxD, maxS, pf; bool phong; };
 
@@ -99,7 +100,7 @@ __device__ __forceinline__ vec3 mis_sample(const MisSurf& h, Rng& rng, vec3& f_r
     if (diffuse) wi = cosine_sample(h.n, rng);
     else wi = lobe_sample(h.wr, h.shin, rng);
     const LobePow lp = mis_lobe_pow(h, wi);
-    if constexpr (E == kEstUnbiased) {
+    if constexpr (E != kEstReference) {
         pdf = mis_pdf_for(h, wi, lp);
         f_r = mis_brdf(h, lp);
     } else {

@@ -1,5 +1,6 @@
 // rs_path.h -- the NEE path tracers: the global-illumination ground truths, one kernel for
-// the two estimators.  The reference's:
+// the three estimators (k_path's E; the third, the unbiased one under a sky, is described at the kernel and in DESIGN.md
+// §3.31, its checker is spath_L in tests/cpp/sky_oracle.c).  The reference's:
 //
 // SimpleGuiDX11::produceStandard (pg/simpleguidx11.cpp:336-357) driving NEEPathIntegrator::integrateImpl2
 // (pg/NEEPathIntegrator.cpp:72-131) with calcGI on: at every path vertex the MIS direct estimate of rs_mis.h
@@ -25,6 +26,7 @@
 // path ends; the per-pixel streams make the result independent of that schedule.
 #pragma once
 #include "rs_mis.h"
+#include "rs_sky.h"
 
 namespace rs {
 
@@ -50,9 +52,28 @@ __device__ __forceinline__ MisSurf path_surf(const DevScene& S, const SurfHit& h
     return h;
 }
 
+// The sky strategy's direct estimate at h (kEstUnbiasedSky): one sky sample from two draws, an any-hit ray from h.pos
+// with no far end, the power heuristic against the BRDF strategy's density on the sampled direction.  The emitters'
+// counterpart is mis_light_part; the two integrate disjoint sets of directions.
+template <int T>
+__device__ __forceinline__ vec3 sky_light_part(const DevScene& S, const FrameConst& F, const SkyLight& K, const MisSurf& h,
+                                               bool alive, Rng& rng, uint32_t& rays) {
+    const float u_row = rng.range(0.0f, 1.0f), u_col = rng.range(0.0f, 1.0f);
+    const SkySample s = sky_sample(S, K, u_row, u_col);
+    const float cI = gmax(dot(s.dir, h.n), 0.0f);
+    const bool ok = alive && s.pdf > 0.0f && cI > 0;
+    rays += ok ? 1u : 0u;
+    const bool occ = trace_any<T>(S, ok, h.pos, s.dir, FLT_MIN + F.tnear_off, FLT_MAX);
+    if (!ok || occ) return mk(0, 0, 0);
+    const LobePow lp = mis_lobe_pow(h, s.dir);
+    const float w = mis_power(s.pdf, mis_pdf_for(h, s.dir, lp));
+    if (!(w > 0.0f)) return mk(0, 0, 0);
+    return dvs(((s.L * w) * mis_brdf(h, lp)) * cI, s.pdf);
+}
+
 template <int T, int E, bool kRows = false>                         // kRows: as k_direct_mis's
 __global__ void __launch_bounds__(kPathBlock) k_path(DevScene S, FrameConst F, PathConst Q, float* fb, CountSlot C,
-                                                       RowSet R) {
+                                                       RowSet R, SkyLight K) {
     // E = kEstReference restates the reference's estimator bit for bit, three biases included.
     // E = kEstUnbiased is the textbook estimator over the same material model, free of the reference's structure: per
     // vertex one light sample with its shadow ray (mis_light_part, unchanged) and one BRDF sample whose ray does both
@@ -65,7 +86,18 @@ __global__ void __launch_bounds__(kPathBlock) k_path(DevScene S, FrameConst F, P
     //   - Russian roulette (bounce > 5, q = min(max(maxc Kd, maxc Ks) of the record, 1)) is drawn after the emitter
     //     test and divides the whole return of the vertex, direct part included: its record is (Ld / q, ...);
     //   - one closest-hit ray per vertex instead of two: two walks per iteration, not three.
-    constexpr bool U = E == kEstUnbiased;
+    // E = kEstUnbiasedSky is kEstUnbiased with the environment as a light.  A direction from a vertex
+    // ends on an emitter, on another surface or in the environment; the emitters keep their two strategies, the
+    // environment gets its own two, and on each domain the weights sum to one:
+    //   - one sky sample per vertex (sky_light_part) when calc_di, use_skybox and the tables' total > 0, drawn after
+    //     the emitter sample and before the BRDF sample; it joins Ld before sanitize and the division by q;
+    //   - a BRDF ray that misses, at any vertex, the last included, brings L_env * power weight against the sky sample's
+    //     density on its direction (weight 1 where there is no sky strategy: bg_color, a sky without light); nothing
+    //     with calc_di off, as the emitters that ray finds count nothing then.
+    // K is read by this instantiation only.
+    constexpr bool U = E != kEstReference;
+    constexpr bool SK = E == kEstUnbiasedSky;
+    const bool sky_on = SK && F.use_sky && K.total > 0;              // the sky strategy exists (uniform)
     extern __shared__ __attribute__((aligned(16))) float path_rec[];
     constexpr int TL = T | TRAV_LANE;               // past the camera vertex every ray is incoherent
     float* const rec = path_rec + threadIdx.x;
@@ -103,6 +135,9 @@ __global__ void __launch_bounds__(kPathBlock) k_path(DevScene S, FrameConst F, P
                 Ld = Ld + mis_light_part<TL>(S, F, h, live, rng, rays);
             } else {
                 Ld = mk(0, 0, 0) + mis_light_part<TL>(S, F, h, live, rng, rays);
+                if constexpr (SK) {
+                    if (sky_on) Ld = Ld + sky_light_part<TL>(S, F, K, h, live, rng, rays);
+                }
             }
         }
         Ld = sanitize(Ld);
@@ -134,7 +169,17 @@ __global__ void __launch_bounds__(kPathBlock) k_path(DevScene S, FrameConst F, P
                 r[7 * kPathBlock] = pdf * q;
             }
             const MatRec mx = load_mat(S, nx.mat);
-            if (go && !nx.hit && (!U || !last)) R = F.use_sky ? sky_texel(S, wi) : F.bg;
+            if constexpr (!SK) {
+                if (go && !nx.hit && (!U || !last)) R = F.use_sky ? sky_texel(S, wi) : F.bg;
+            } else if (go && !nx.hit && Q.di) {                     // the BRDF strategy's estimate of the environment
+                if (sky_on) {
+                    float p_sky;
+                    const vec3 Le = sky_lookup(S, K, wi, p_sky);
+                    R = Le * mis_power(pdf, p_sky);
+                } else {
+                    R = F.use_sky ? sky_texel(S, wi) : F.bg;
+                }
+            }
             if (go && nx.hit) {
                 const float maxT = gmax(maxc(mx.kd), maxc(mx.ks));   // the record's colours, not the mapped ones
                 const bool rr = b + 1 > 5 && Q.rr;

@@ -30,9 +30,9 @@ __device__ __forceinline__ vec3 tex_texel(const DevScene& S, int t, int x, int y
 }
 
 // Texture::getTexelBilinear (pg/Texture.cpp:170-194); glm::mix(x, y, a) = x * (1 - a) + y * a
-__device__ __forceinline__ vec3 tex_bilinear(const DevScene& S, int t, float u, float v, bool repeat) {
-    const int4 a = S.texd[2 * t];
-    const float pxc = u * (float)a.y, pyc = (1.0f - v) * (float)a.z;
+// the body, from the texel coordinates (pxc, pyc) = (u w, (1 - v) h): the entry of callers that have them already
+// (rs_sky.h: a sampled sky position)
+__device__ __forceinline__ vec3 tex_bilinear_px(const DevScene& S, int t, float pxc, float pyc, bool repeat) {
     const float fx = floorf(pxc), fy = floorf(pyc);
     const float tx = pxc - fx, ty = pyc - fy;
     const vec3 q00 = tex_texel(S, t, (int)fx, (int)fy, repeat);
@@ -43,13 +43,21 @@ __device__ __forceinline__ vec3 tex_bilinear(const DevScene& S, int t, float u, 
     const vec3 x2 = q01 * (1.0f - tx) + q11 * tx;
     return x1 * (1.0f - ty) + x2 * ty;
 }
+__device__ __forceinline__ vec3 tex_bilinear(const DevScene& S, int t, float u, float v, bool repeat) {
+    const int4 a = S.texd[2 * t];
+    return tex_bilinear_px(S, t, u * (float)a.y, (1.0f - v) * (float)a.z, repeat);
+}
 
 // SphericalMap::getTexel (pg/SphericalMap.cpp:10-14): INVPI = 1.0 / M_PI is a double, so both
 // coordinates are finished in double; the sky texture is BILINEAR + CLAMP_TO_EDGE (Texture.h:27)
-__device__ __forceinline__ vec3 sky_texel(const DevScene& S, vec3 dir) {
+__device__ __forceinline__ void sky_uv(vec3 dir, float& x, float& y) {
     const double invpi = 1.0 / 3.14159265358979323846;
-    const float x = (float)(0.5f + (double)(0.5f * atan2f(dir.y, dir.x)) * invpi);
-    const float y = (float)(1.0f - (double)acosf(dir.z) * invpi);
+    x = (float)(0.5f + (double)(0.5f * atan2f(dir.y, dir.x)) * invpi);
+    y = (float)(1.0f - (double)acosf(dir.z) * invpi);
+}
+__device__ __forceinline__ vec3 sky_texel(const DevScene& S, vec3 dir) {
+    float x, y;
+    sky_uv(dir, x, y);
     return tex_bilinear(S, S.sky, x, y, false);
 }
 

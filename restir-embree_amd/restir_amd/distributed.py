@@ -157,7 +157,7 @@ class GpuTileBackend:
     def render_ground_truth_rows(self, scene, camera, params, frame_index, spp, path_kwargs, rows):
         """The rows of the set (strip_rows, stride, phase) of a ground-truth frame, in a full-frame-sized (H * W * 3)
         tensor over the context's framebuffer; path_kwargs None: the MIS direct-light ground truth, else
-        Renderer.render_path's keywords (max_bounces, ..., unbiased)."""
+        Renderer.render_path's keywords (max_bounces, ..., unbiased, sky_light)."""
         if path_kwargs is None:
             self.r.render_direct_mis(scene, camera, params, frame_index, spp, copy_out=False, rows=rows)
         else:
@@ -407,16 +407,26 @@ class TiledRenderer:
     # ---- ground truths: interleaved 16-row strips (strip_rows_of), no halo, no bands
     def render_path(self, scene, camera, params, frame_index: int, spp: int = 1, max_bounces: int = 5,
                     russian_roulette: bool = True, calc_di: bool = True, calc_gi: bool = True, unbiased: bool = False,
-                    gather: bool = True):
+                    gather: bool = True, sky_light: bool = False):
         """One path-traced ground-truth frame (Renderer.render_path) across the ranks: this rank renders the strips
         strip_rows_of(H, rank, world); with gather the full (H, W, 3) frame is returned on rank 0, bit for bit a
         single renderer's (None elsewhere).  Without gather: this rank's full-frame-sized tensor, its strips valid."""
+        if sky_light and not unbiased:
+            raise ValueError("sky_light needs unbiased=True: the reference's estimators keep their sky handling")
         kw = dict(max_bounces=max_bounces, russian_roulette=russian_roulette, calc_di=calc_di, calc_gi=calc_gi,
                   unbiased=unbiased)
+        if sky_light:
+            kw["sky_light"] = True
         return self._ground_truth(scene, camera, params, frame_index, spp, kw, gather)
 
-    def render_direct_mis(self, scene, camera, params, frame_index: int, spp: int = 1, gather: bool = True):
-        """The MIS direct-light ground truth (Renderer.render_direct_mis) the same way."""
+    def render_direct_mis(self, scene, camera, params, frame_index: int, spp: int = 1, gather: bool = True,
+                          unbiased: bool = False, sky_light: bool = False):
+        """The MIS direct-light ground truth (Renderer.render_direct_mis) the same way; unbiased, sky_light: its."""
+        if sky_light and not unbiased:
+            raise ValueError("sky_light needs unbiased=True: the reference's estimators keep their sky handling")
+        if unbiased:
+            return self.render_path(scene, camera, params, frame_index, spp, calc_gi=False, unbiased=True, gather=gather,
+                                    sky_light=sky_light)
         return self._ground_truth(scene, camera, params, frame_index, spp, None, gather)
 
     def _ground_truth(self, scene, camera, params, frame_index, spp, path_kwargs, gather):

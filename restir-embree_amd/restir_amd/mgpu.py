@@ -16,7 +16,7 @@ import ctypes
 import numpy as np
 
 from .params import PathParams
-from .renderer import (CameraDesc, GT_DIRECT_MIS, GT_PATH, GT_PATH_UNBIASED, PassTimes, RestirError, camera_desc,
+from .renderer import (CameraDesc, GT_DIRECT_MIS, GT_PATH, GT_PATH_UNBIASED, PassTimes, gt_estimator, RestirError, camera_desc,
                        load_library)
 
 ID_BYTES = 128
@@ -129,21 +129,24 @@ class MultiGpuFrame:
 
     def render_path(self, scenes, camera, params, frame_index: int, spp: int = 1, max_bounces: int = 5,
                     russian_roulette: bool = True, calc_di: bool = True, calc_gi: bool = True, unbiased: bool = False,
-                    gather: bool = True, copy_out: bool = False, timed: bool = False):
+                    gather: bool = True, copy_out: bool = False, timed: bool = False, sky_light: bool = False):
         """One path-traced ground-truth frame on all ranks (rs_mgpu_render_ground_truth): rank r renders the 16-row
         strips r, r + world, ...; with gather they land in rank 0's framebuffer, bit for bit one context's
         Renderer.render_path frame, and post_frame on rank 0's renderer processes all rows.  copy_out (rank 0)
-        returns the (H, W, 3) frame (synchronous)."""
+        returns the (H, W, 3) frame (synchronous).  unbiased, sky_light: Renderer.render_path's."""
         pp = PathParams(max_bounces, russian_roulette, calc_di, calc_gi)
-        return self._ground_truth(scenes, camera, params, GT_PATH_UNBIASED if unbiased else GT_PATH, pp, frame_index,
+        return self._ground_truth(scenes, camera, params, gt_estimator(unbiased, sky_light), pp, frame_index,
                                   spp, gather, copy_out, timed)
 
     def render_direct_mis(self, scenes, camera, params, frame_index: int, spp: int = 1, unbiased: bool = False,
-                          gather: bool = True, copy_out: bool = False, timed: bool = False):
-        """The MIS direct-light ground truth the same way (unbiased: render_path(unbiased=True, calc_gi=False))."""
+                          gather: bool = True, copy_out: bool = False, timed: bool = False, sky_light: bool = False):
+        """The MIS direct-light ground truth the same way (unbiased: render_path(unbiased=True, calc_gi=False),
+        sky_light with it)."""
+        if sky_light and not unbiased:
+            raise ValueError("sky_light needs unbiased=True: the reference's estimators keep their sky handling")
         if unbiased:
             return self.render_path(scenes, camera, params, frame_index, spp, calc_gi=False, unbiased=True,
-                                    gather=gather, copy_out=copy_out, timed=timed)
+                                    gather=gather, copy_out=copy_out, timed=timed, sky_light=sky_light)
         return self._ground_truth(scenes, camera, params, GT_DIRECT_MIS, None, frame_index, spp, gather, copy_out, timed)
 
     def frame_device_ptr(self) -> int:

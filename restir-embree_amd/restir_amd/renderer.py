@@ -42,12 +42,19 @@ EXPORTED_SYMBOLS = [
     "rs_denoiser_execute", "rs_denoise_frame", "rs_context_set_denoiser", "rs_denoiser_set_timing",
     "rs_denoiser_last_ms", "rs_denoiser_layer_ms", "rs_denoiser_get_scale", "rs_denoiser_dump", "rs_denoiser_destroy",
     "rs_render_path", "rs_debug_bvh_tree", "rs_debug_light_tables", "rs_render_path_unbiased",
-    "rs_render_ground_truth_rows", "rs_mgpu_render_ground_truth",
+    "rs_render_ground_truth_rows", "rs_mgpu_render_ground_truth", "rs_render_path_sky", "rs_debug_sky_tables",
 ]
 
 # ground-truth estimators and the strip height of their row sets (include/restir_c.h RS_GT_*, RS_ROW_STRIP)
-GT_DIRECT_MIS, GT_PATH, GT_PATH_UNBIASED = 0, 1, 2
+GT_DIRECT_MIS, GT_PATH, GT_PATH_UNBIASED, GT_PATH_UNBIASED_SKY = 0, 1, 2, 4
 ROW_STRIP = 16
+
+
+def gt_estimator(unbiased: bool, sky_light: bool = False) -> int:
+    """The RS_GT_* id of a path estimator from render_path's keywords"""
+    if sky_light and not unbiased:
+        raise ValueError("sky_light needs unbiased=True: the reference's estimators keep their sky handling")
+    return GT_PATH_UNBIASED_SKY if sky_light else (GT_PATH_UNBIASED if unbiased else GT_PATH)
 
 
 class RowSet(ctypes.Structure):
@@ -222,6 +229,9 @@ def load_library(path: str = LIB_PATH):
     L.rs_render_path.argtypes = [vp, vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(FrameParams),
                                  ctypes.POINTER(PathParams), u32, u32, fp, ctypes.POINTER(PassTimes)]
     L.rs_render_path_unbiased.argtypes = L.rs_render_path.argtypes
+    if hasattr(L, "rs_render_path_sky"):         # (absent from earlier builds, which A/Bs load)
+        L.rs_render_path_sky.argtypes = L.rs_render_path.argtypes
+        L.rs_debug_sky_tables.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), vp, vp]
     L.rs_render_ground_truth_rows.argtypes = [vp, vp, ctypes.POINTER(CameraDesc), ctypes.POINTER(FrameParams), i32,
                                               ctypes.POINTER(PathParams), u32, u32, ctypes.POINTER(RowSet), fp,
                                               ctypes.POINTER(PassTimes)]
@@ -412,6 +422,19 @@ class Scene:
         r._check(r.lib.rs_debug_light_tables(self.h, ctypes.byref(ne), em.ctypes.data_as(ctypes.c_void_p),
                                              cdf.ctypes.data_as(ctypes.c_void_p), guide.ctypes.data_as(ctypes.c_void_p)))
         return em, cdf, guide
+
+    def sky_tables(self):
+        """Test hook (rs_debug_sky_tables): the sampling tables of the scene's sky, built if need be, as (row_cdf (h, w)
+        uint32 -- per row the inclusive prefix sum of the cells' integer weights --, marginal (h,) uint64 -- the
+        inclusive prefix sum of the row totals)."""
+        r = self.renderer
+        w, h = ctypes.c_uint32(), ctypes.c_uint32()
+        r._check(r.lib.rs_debug_sky_tables(self.h, ctypes.byref(w), ctypes.byref(h), None, None))
+        cdf = np.zeros((h.value, w.value), np.uint32)
+        marg = np.zeros(h.value, np.uint64)
+        r._check(r.lib.rs_debug_sky_tables(self.h, ctypes.byref(w), ctypes.byref(h), cdf.ctypes.data_as(ctypes.c_void_p),
+                                           marg.ctypes.data_as(ctypes.c_void_p)))
+        return cdf, marg
 
     def close(self):
         if self.h:
@@ -643,15 +666,17 @@ class Renderer:
 
     def render_direct_mis(self, scene: Scene, camera, params: FrameParams, frame_index: int = 0, spp: int = 1,
                           copy_out: bool = True, timed: bool = False, unbiased: bool = False,
-                          rows=None) -> np.ndarray | None:
+                          rows=None, sky_light: bool = False) -> np.ndarray | None:
         """MIS direct-light ground truth (rs_render_direct_mis; DirectMISIntegrator, calcGI off): spp
         samples per pixel into the framebuffer.  Accumulate frames with post_frame(accumulate=True) for a
         converged reference.  timed=True fills last_times (shade_ms = the launch, rays).  unbiased=True: the
-        unbiased estimator's direct light instead (render_path(unbiased=True, calc_gi=False)).  rows: as
+        unbiased estimator's direct light instead (render_path(unbiased=True, calc_gi=False)).  rows, sky_light: as
         render_path's."""
+        if sky_light and not unbiased:
+            raise ValueError("sky_light needs unbiased=True: the reference's estimators keep their sky handling")
         if unbiased:
             return self.render_path(scene, camera, params, frame_index, spp, calc_gi=False, copy_out=copy_out,
-                                    timed=timed, unbiased=True, rows=rows)
+                                    timed=timed, unbiased=True, rows=rows, sky_light=sky_light)
         if rows is not None:
             return self._render_rows(scene, camera, params, GT_DIRECT_MIS, None, frame_index, spp, rows, copy_out, timed)
         cam = camera_desc(camera)
@@ -664,22 +689,28 @@ class Renderer:
     def render_path(self, scene: Scene, camera, params: FrameParams, frame_index: int = 0, spp: int = 1,
                     max_bounces: int = 5, russian_roulette: bool = True, calc_di: bool = True, calc_gi: bool = True,
                     copy_out: bool = True, timed: bool = False, unbiased: bool = False,
-                    rows=None) -> np.ndarray | None:
+                    rows=None, sky_light: bool = False) -> np.ndarray | None:
         """NEE path tracer (rs_render_path; NEEPathIntegrator::integrateImpl2 with the MIS direct integrator):
         direct plus indirect light up to max_bounces, spp samples per pixel into the framebuffer.  calc_gi=False
         is render_direct_mis bit for bit.  Accumulate frames with post_frame(accumulate=True).  timed=True fills
         last_times (shade_ms = the launch, rays).  unbiased=True: rs_render_path_unbiased, the textbook NEE + MIS
         estimator over the same material model -- the reference's estimator is dark on materials with kd and ks;
-        params.normal_offset is not used by it.  rows=(strip_rows, stride, phase): rs_render_ground_truth_rows --
+        params.normal_offset is not used by it.  sky_light=True (with unbiased): rs_render_path_sky, the same with the
+        environment as a light -- the sky is sampled from tables of its texels and counts at every vertex, the last
+        included; rs_render_path_unbiased leaves a surface under the sky black with calc_gi off and finds a sun only
+        by chance.  rows=(strip_rows, stride, phase): rs_render_ground_truth_rows --
         only the rows y with (y // strip_rows) % stride == phase are rendered, bit for bit the full frame's, and the
         other rows of the framebuffer keep their contents."""
+        if sky_light and not unbiased:
+            raise ValueError("sky_light needs unbiased=True: the reference's estimators keep their sky handling")
         pp = PathParams(max_bounces, russian_roulette, calc_di, calc_gi)
         if rows is not None:
-            return self._render_rows(scene, camera, params, GT_PATH_UNBIASED if unbiased else GT_PATH, pp, frame_index,
+            return self._render_rows(scene, camera, params, gt_estimator(unbiased, sky_light), pp, frame_index,
                                      spp, rows, copy_out, timed)
         cam = camera_desc(camera)
         out = self.frame_data.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if copy_out else None
-        fn = self.lib.rs_render_path_unbiased if unbiased else self.lib.rs_render_path
+        fn = self.lib.rs_render_path_sky if sky_light else (
+            self.lib.rs_render_path_unbiased if unbiased else self.lib.rs_render_path)
         self._check(fn(self.h, scene.h, ctypes.byref(cam), ctypes.byref(params), ctypes.byref(pp),
                        int(frame_index), int(spp), out, ctypes.byref(self.last_times) if timed else None))
         return self.frame_data if copy_out else None

@@ -6,10 +6,12 @@
 //   restir_render [--obj file.obj] [--w 1920 --h 1080] [--frames 10] [--area 32] [--brdf 1]
 //                 [--spatial k] [--temporal] [--out frame.pfm] [--eye x y z --at x y z --fov deg]
 //                 [--bench] [--ranks N [--compare]] [--denoise weights.tza [--png display.png]]
-//                 [--path SPP [--bounces N] [--unbiased]]
+//                 [--path SPP [--bounces N] [--unbiased [--sky-light]]] [--sky file]
 // --path SPP: the frames are produceStandard's instead -- the NEE path tracer (direct + indirect light up to N
 // bounces, default 5) at SPP samples per pixel, accumulated like the ReSTIR frames; --out writes the last.
 // --unbiased (only with --path): the unbiased NEE + MIS estimator (rs_render_path_unbiased) instead of the reference's.
+// --sky FILE: an equirect sky (.hdr / .pfm / .ppm / .png; rs_scene_load_sky) with use_skybox on.
+// --sky-light (only with --path SPP --unbiased): the environment as a light (rs_render_path_sky).
 // --bench: the drop-in throughput -- frames/s of produceRestir with frame_data landing in host memory
 // every frame, pipelined (pipelineDepth 2 and 1: readbacks overlapping the next frames, timePasses off)
 // and with the reference's synchronous semantics; one JSON line.
@@ -44,9 +46,9 @@ static void write_pfm(const std::string& path, int W, int H, const float* rgb) {
 }
 
 int main(int argc, char** argv) {
-    std::string obj, out, denoise_w, png;
+    std::string obj, out, denoise_w, png, sky;
     int W = 512, H = 512, frames = 5;
-    bool bench = false, cam_set = false, compare = false, unbiased = false;
+    bool bench = false, cam_set = false, compare = false, unbiased = false, sky_light = false;
     int ranks = 0, path_spp = 0, bounces = 5;
     float eye[3] = {0, 0, 0}, at[3] = {0, 0, 0}, fov = 40.0f;
     restir::Renderer* rp = nullptr;
@@ -71,6 +73,8 @@ int main(int argc, char** argv) {
         else if (a == "--path") path_spp = std::atoi(next());
         else if (a == "--bounces") bounces = std::atoi(next());
         else if (a == "--unbiased") unbiased = true;
+        else if (a == "--sky") sky = next();
+        else if (a == "--sky-light") sky_light = true;
         else if (a == "--eye") { for (float& v : eye) v = (float)std::atof(next()); cam_set = true; }
         else if (a == "--at") { for (float& v : at) v = (float)std::atof(next()); cam_set = true; }
         else if (a == "--fov") fov = (float)std::atof(next());
@@ -79,8 +83,13 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "restir_render: --unbiased is valid only with --path SPP\n");
         return 1;
     }
-    // Raytracer::LoadScene: the OBJ file, or the C1 Cornell box built in memory
-    auto load = [&](restir::Renderer& r) {
+    if (sky_light && !(unbiased && path_spp > 0)) {
+        std::fprintf(stderr, "restir_render: --sky-light is valid only with --path SPP --unbiased\n");
+        return 1;
+    }
+    if (!sky.empty()) prm.use_skybox = 1;
+    // Raytracer::LoadScene: the OBJ file, or the C1 Cornell box built in memory; then the sky, if one is given
+    auto load_geometry = [&](restir::Renderer& r) {
         if (!obj.empty()) {
             r.LoadScene(obj);
             r.camera_ = restir::Camera(1.878f, -7.724f, 1.602f, 0, 0, 0, 55.0f);   // tutorial_3 camera
@@ -106,6 +115,10 @@ int main(int argc, char** argv) {
         r.LoadScene(meshes, {white, light});
         r.camera_ = restir::Camera(0.0f, -3.9f, 1.0f, 0.0f, 0.0f, 1.0f, 40.0f);
     };
+    auto load = [&](restir::Renderer& r) {
+        load_geometry(r);
+        if (!sky.empty()) r.LoadSky(sky);
+    };
     try {
         if (ranks > 0) {
             int ndev = 1;
@@ -118,6 +131,7 @@ int main(int argc, char** argv) {
             mg.samplesPerPixel = (uint32_t)std::max(path_spp, 1);
             mg.pathParams.max_bounces = bounces;
             mg.unbiasedEstimator = unbiased;
+            mg.skyLight = sky_light;
             // one frame of either renderer: the ReSTIR frame, or with --path the ground truth
             auto produce = [&](auto& r) { if (path_spp > 0) r.produceStandard(); else r.produceRestir(); };
             std::unique_ptr<restir::Renderer> one;
@@ -129,6 +143,7 @@ int main(int argc, char** argv) {
                 one->samplesPerPixel = mg.samplesPerPixel;
                 one->pathParams = mg.pathParams;
                 one->unbiasedEstimator = unbiased;
+                one->skyLight = sky_light;
             }
             bool same = true;
             for (int f = 0; f < frames; ++f) {
@@ -180,6 +195,7 @@ int main(int argc, char** argv) {
         r.samplesPerPixel = (uint32_t)path_spp;
         r.pathParams.max_bounces = bounces;
         r.unbiasedEstimator = unbiased;
+        r.skyLight = sky_light;
         for (int f = 0; f < frames; ++f) {
             if (path_spp > 0) {
                 r.produceStandard();
