@@ -437,7 +437,11 @@ typedef struct {
     double mac_per_pixel;      /* multiply-accumulates per (padded) input pixel */
 } rs_denoiser_info;
 typedef struct {
-    float input_scale;         /* oidn "inputScale": <= 0 or NaN = auto-exposure (OIDN's default) */
+    float input_scale;         /* oidn "inputScale": <= 0 or NaN = auto-exposure (OIDN's default): 0.18 over the
+                                * geometric mean of the <= 16x16-pixel bins' mean luminance, of the colour
+                                * sanitised as the input transform sanitises it (per channel NaN -> 0, then
+                                * clamped to [0, FLT_MAX]); bins at or below 1e-8 skipped, 1 when none is left.
+                                * A non-finite or negative pixel neither blackens the frame nor drops its bin. */
     int32_t hdr;               /* oidn "hdr": must be 1 (the reference sets true) */
 } rs_denoise_params;
 /* Host only (no device work): parse + check an archive against the UNet topology. */

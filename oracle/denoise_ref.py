@@ -20,7 +20,12 @@ filter -- parity UNPINNED against OIDN itself (no fixture or output of it exists
     upsampling before dec_conv4a/3a/2a/1a, concatenation [upsampled, skip], dec_conv0 linear;
   * output: max(x, 0) through the inverse transfer function, divided by inputScale;
   * auto-exposure: key 0.18 over the geometric mean of the mean luminance of <= 16x16-pixel bins
-    (bins with mean luminance <= 1e-8 skipped).
+    (bins with mean luminance <= 1e-8 skipped; 1 when none is left).  The luminance is taken of the
+    sanitised colour, clamp(nan_to_zero(c), 0, FLT_MAX) per channel, as OIDN 2.x's auto-exposure kernel
+    does -- recalled, not read: OIDN's source is not available here, so this is UNPINNED like the rest.
+    Without it the exposure came from another image than the one the input transform sanitises: one +Inf
+    channel made a bin's mean inf and the scale 0, i.e. the whole denoised frame black, and a NaN or a
+    large negative pixel dropped its bin from the mean.
 The GPU implementation (csrc/rs_denoise.hip) is checked against this module with the same weights.
 `quantize=True` rounds weights and every stored activation to float16, as the GPU stores them, so the
 two differ only by float32 accumulation order (tight tolerance); without it the comparison includes the
@@ -73,21 +78,45 @@ def luminance(c):
             + np.float32(0.072169) * c[..., 2]).astype(np.float32)
 
 
+FLT_MAX = np.finfo(np.float32).max
+
+
 def autoexposure(color: np.ndarray) -> np.float32:
-    """key / exp2(mean log2 L) over ceil(H/16) x ceil(W/16) bins (bin b spans [b*H/n, (b+1)*H/n))."""
+    """key / exp2(mean log2 L) over ceil(H/16) x ceil(W/16) bins (bin b spans [b*H/n, (b+1)*H/n)) of the
+    sanitised colour: per channel NaN -> 0, then clamped to [0, FLT_MAX] -- the identity on a finite,
+    non-negative image.  A pixel's luminance is held at FLT_MAX and a bin sums in float64, so a bin full of
+    FLT_MAX pixels has the mean FLT_MAX, not inf.
+
+    The log2 sum is float32, as on the GPU.  A float32 near 100 is spaced 7.6e-6, which would cost the scale up to
+    5e-6 for a bin mean of 1e30 or FLT_MAX, so a bin mean L >= 2**32 is range-reduced: L = m 2**e (frexp, exact),
+    log2 m in [-1, 0) joins the float32 sum and e an exact integer sum.  While every bin mean is below 2**32 no
+    exponent is taken and every operation is the one this function always ran: the scale keeps its bits."""
     H, W = color.shape[:2]
     nbh, nbw = -(-H // 16), -(-W // 16)
-    lum = luminance(color)
-    s, n = np.float32(0.0), 0
+    with np.errstate(over="ignore"):
+        lum = np.minimum(luminance(_sanitize(color, 0.0, FLT_MAX)), FLT_MAX)
+    s, n, E = np.float32(0.0), 0, 0
     for i in range(nbh):
         y0, y1 = i * H // nbh, (i + 1) * H // nbh
         for j in range(nbw):
             x0, x1 = j * W // nbw, (j + 1) * W // nbw
-            L = np.float32(lum[y0:y1, x0:x1].astype(np.float64).sum()) / np.float32((y1 - y0) * (x1 - x0))
+            S, k = lum[y0:y1, x0:x1].astype(np.float64).sum(), (y1 - y0) * (x1 - x0)
+            # float32 sum over float32 count as before wherever the sum fits float32; past it (pixels near FLT_MAX
+            # only) the float64 quotient
+            L = np.float32(S) / np.float32(k) if S <= float(FLT_MAX) else np.float32(S / k)
             if L > np.float32(1e-8):
-                s += np.float32(math.log2(L))
+                if L >= np.float32(2.0 ** 32):
+                    m, e = math.frexp(float(L))
+                    s += np.float32(math.log2(m))
+                    E += e
+                else:
+                    s += np.float32(math.log2(L))
                 n += 1
-    return np.float32(0.18) / np.float32(2.0 ** (s / n)) if n else np.float32(1.0)
+    if not n:
+        return np.float32(1.0)
+    if E == 0:
+        return np.float32(0.18) / np.float32(2.0 ** (s / n))
+    return np.float32(float(np.float32(0.18)) / 2.0 ** ((float(s) + E) / n))    # float64: 2**x may pass FLT_MAX
 
 
 def _sanitize(x, lo, hi):

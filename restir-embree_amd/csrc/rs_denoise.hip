@@ -34,6 +34,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -607,10 +608,13 @@ __global__ void __launch_bounds__(256) k_dn_input(InArgs a) {
     d[1] = *(const uint4*)&v[8];
 }
 
-// bins of <= 16x16 pixels: mean luminance -> log2 (NaN marks a bin at or below eps)
+// bins of <= 16x16 pixels: mean luminance -> log2 (NaN marks a bin at or below eps).  The colour is read through
+// the sanitisation the input transform applies (NaN -> 0, then [0, FLT_MAX]), so one non-finite or negative pixel
+// cannot take the exposure -- and with it the whole frame -- to 0 or drop its bin; a pixel's luminance stays at
+// FLT_MAX at most and the bin sums in double, so 256 pixels at FLT_MAX do not overflow
 __global__ void __launch_bounds__(256) k_dn_ae_bins(const float* color, int cst, int H, int W, int nbh, int nbw,
                                                       float* binlog) {
-    __shared__ float s[256];
+    __shared__ double s[4];
     const int b = blockIdx.x, bi = b / nbw, bj = b - bi * nbw;
     const int y0 = (int)((long long)bi * H / nbh), y1 = (int)((long long)(bi + 1) * H / nbh);
     const int x0 = (int)((long long)bj * W / nbw), x1 = (int)((long long)(bj + 1) * W / nbw);
@@ -620,16 +624,16 @@ __global__ void __launch_bounds__(256) k_dn_ae_bins(const float* color, int cst,
     if (t < n) {
         const size_t q = (size_t)(y0 + t / bw) * W + (x0 + t % bw);
         const float* c = color + q * cst;
-        L = 0.212671f * c[0] + 0.715160f * c[1] + 0.072169f * c[2];
+        const float r = clampf(c[0], 0.0f, FLT_MAX), g = clampf(c[1], 0.0f, FLT_MAX), bl = clampf(c[2], 0.0f, FLT_MAX);
+        L = fminf(0.212671f * r + 0.715160f * g + 0.072169f * bl, FLT_MAX);
     }
-    s[t] = L;
+    double v = (double)L;                              // each wave's sum by butterfly, the four waves' through LDS
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((t & 63) == 0) s[t >> 6] = v;
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (t < w) s[t] += s[t + w];
-        __syncthreads();
-    }
     if (t == 0) {
-        const float m = s[0] / (float)n;
+        const float m = (float)(((s[0] + s[1]) + (s[2] + s[3])) / (double)n);
         binlog[b] = m > 1e-8f ? log2f(m) : __builtin_nanf("");
     }
 }

@@ -30,16 +30,11 @@ torch = pytest.importorskip("torch")
 from restir_amd import Renderer, metric_params, scenes, tza  # noqa: E402
 from restir_amd.denoise import Denoiser  # noqa: E402
 
+import denoise_cases as C  # noqa: E402  (the images, shared with the CPU tests)
 import denoise_ref as ref  # noqa: E402  (oracle/, test infrastructure)
 
 
-def _images(H, W, seed=0):
-    rng = np.random.default_rng(seed)
-    color = rng.lognormal(-0.5, 1.2, (H, W, 3)).astype(np.float32)
-    albedo = rng.uniform(0, 1, (H, W, 3)).astype(np.float32)
-    n = rng.standard_normal((H, W, 3)).astype(np.float32)
-    n /= np.linalg.norm(n, axis=-1, keepdims=True)
-    return color, albedo, n
+_images = C.benign_images       # lognormal colour, uniform albedo, unit normals; the hostile ones: test_gpu_denoise_inputs.py
 
 
 def _err(got, want, scale=1.0):
@@ -88,7 +83,14 @@ def test_every_layer_matches_float64(ctx, monkeypatch, H, W, fill):
     largest n-tile count <= 4 that divides its n-tiles -- k_conv3 with 1, 2, 3 and 4 n-tiles, storing and
     pooling, where the default at these sizes runs nearly every layer with 1."""
     r, d, w = ctx
-    color, albedo, normal = _images(H, W, seed=31 + H)
+    check_every_layer(r, d, w, monkeypatch, _images(H, W, seed=31 + H), fill)
+
+
+def check_every_layer(r, d, w, monkeypatch, images, fill):
+    """The per-convolution comparison of the module docstring on `images` at the input scale 0.9 (shared with
+    tests/test_gpu_denoise_inputs.py, which feeds it hostile images).  Returns the output and the dumped tensors."""
+    color, albedo, normal = images
+    H, W = color.shape[:2]
     if fill is not None:
         monkeypatch.setenv("RESTIR_DN_FILL", fill)
         d = Denoiser(r, w)
@@ -123,6 +125,7 @@ def test_every_layer_matches_float64(ctx, monkeypatch, H, W, fill):
         print(f"{name}: {off.mean() * 100:.3f} % of {diff.size} elements differ, max {float((diff / bound).max()):.3f} of the bound")
         assert (diff <= bound).all(), (name, float((diff / bound).max()))
         assert off.mean() <= 0.02, (name, float(off.mean()))
+    return got, dumps
 
 
 def test_channel_split_bit_identical(ctx, monkeypatch):
@@ -146,7 +149,7 @@ def test_channel_split_bit_identical(ctx, monkeypatch):
     assert np.array_equal(o0, o1)
 
 
-@pytest.mark.parametrize("H,W,grid", [(48, 64, "2"), (37, 83, "3"), (540, 960, None), (1080, 1920, None)])
+@pytest.mark.parametrize("H,W,grid", [(48, 64, "2"), (37, 83, "3"), (83, 37, "2"), (540, 960, None), (1080, 1920, None)])
 def test_pipelined_conv_bit_identical(monkeypatch, H, W, grid):
     """k_conv3p (the persistent LDS-DMA pipeline, csrc/rs_denoise.hip) against k_conv3 on the layers it runs
     (dec_conv2a / 2b / 1a): the same k-steps in the same order on the same MFMA, so every tensor is bit-identical.
