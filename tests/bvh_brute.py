@@ -381,10 +381,69 @@ def anyhit_rays(cls, seed=2, n=1024, n_axis=1024):
 
 
 def scene_from_positions(pos):
-    """a scenes.Scene of the Cornell material 0 over (T, 9) positions (test_gpu_wide._scene_from_positions)"""
+    """a scenes.Scene of the Cornell material 0 over (T, 9) positions"""
     from restir_amd import scenes
     base = scenes.cornell_box(8)
     pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 9)
     n = pos.shape[0]
     nrm = np.tile(np.array([0, 0, 1] * 3, np.float32), (n, 1))
     return scenes.Scene(pos, nrm, np.zeros(n, np.uint32), base.materials[:1], base.camera)
+
+
+# ---------------------------------------------------------------------------------------------- the trees and their cases
+# tree setting -> (RESTIR_BVH, RESTIR_WIDE): {PLOC (default), the Karras LBVH} x {8-wide tree live, switched off}
+TREES = {"ploc_wide": (None, None), "ploc_skip": (None, "off"), "lbvh_wide": ("lbvh", None), "lbvh_skip": ("lbvh", "off")}
+
+
+def soup32(n, seed, dup=0):
+    """tests/test_gpu_wide.py's soup, in float32 throughout; the first `dup` triangles coincide"""
+    rng = np.random.default_rng(seed)
+    c = rng.uniform(-1, 1, (n, 1, 3)).astype(np.float32) * np.array([4, 2, 1.5], np.float32)
+    p = (c + rng.normal(scale=0.05, size=(n, 3, 3)).astype(np.float32)).reshape(n, 9)
+    if dup:
+        p[:dup] = p[0]                   # coincident triangles: every centroid equal in a > 256-triangle node
+    return p
+
+
+def chain(n, ratio):
+    """n triangles side by side along x, each `ratio` x the size of the previous: a binned / swept SAH split peels
+    off the largest triangle at every level, so the source tree is a chain of depth n - 1 (the SAH-optimal 8-wide
+    collapse of 100 such triangles needs exactly 8 levels; of 110, more than the walk's group stack holds)"""
+    pos, x = [], 0.0
+    for i in range(n):
+        sz = ratio ** i
+        pos.append([x, 0.0, 0.0, x + sz, 0.0, 0.0, x, sz, 0.0])
+        x += sz
+    return np.array(pos, np.float32)
+
+
+def nonfinite_scene():
+    """a soup with one NaN and one infinite coordinate: the scene loads without a wide tree"""
+    p = soup32(800, 5)
+    p[17, 4] = np.nan
+    p[401, 0] = np.inf
+    return scene_from_positions(p)
+
+
+def depth8_scene():
+    """a chain whose wide tree has exactly the walk's stack depth"""
+    return scene_from_positions(chain(100, 1.5))
+
+
+def wide_lib():
+    """tests/cpp/wide_harness.cpp (rs_wide.h on the host), built on first use"""
+    import ctypes
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = os.path.join(root, "tests", "cpp", "wide_harness.cpp")
+    hdr = os.path.join(root, "restir-embree_amd", "csrc", "rs_wide.h")
+    so = os.path.join(root, "oracle", "_build", "libwide_harness.so")
+    os.makedirs(os.path.dirname(so), exist_ok=True)
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", so, src])
+    L = ctypes.CDLL(so)
+    L.wide_check.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.c_char_p, ctypes.c_int,
+                             ctypes.c_int]
+    L.wide_query.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    return L

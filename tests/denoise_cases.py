@@ -1,6 +1,7 @@
 """The denoiser's hostile inputs: images, shapes and float64 definitions shared by tests/test_denoise.py (the CPU
 reference, oracle/denoise_ref.py) and tests/test_gpu_denoise_inputs.py (csrc/rs_denoise.hip).  TEST
-INFRASTRUCTURE ONLY; nothing here is imported from denoise_ref, so a mistake there is not repeated here.
+INFRASTRUCTURE ONLY; the images and definitions import nothing from denoise_ref, so a mistake there is not repeated here
+(the GPU tests' shared steps at the end do use it: they compare against it).
 
 Real frames are not lognormal: a Cornell frame is mostly exact zeros, a primary miss carries a zero normal, and a
 bad material can put Inf or NaN into a pixel's radiance.  What the denoiser promises for them:
@@ -14,6 +15,7 @@ bad material can put Inf or NaN into a pixel's radiance.  What the denoiser prom
   sanitised(color, albedo, normal)
   autoexposure64(color)           the auto-exposure from its definition, in float64
   assert_scale_in_range(color)    the condition on an end-to-end case (see there)
+  run, pu_err, check_every_layer  one execute on the GPU, the PU-domain error, the per-convolution comparison
 """
 from __future__ import annotations
 
@@ -185,3 +187,65 @@ def assert_scale_in_range(color) -> float:
     s = autoexposure64(color)
     assert SCALE_RANGE[0] <= s <= SCALE_RANGE[1], s
     return s
+
+
+# ---------------------------------------------------------------- the GPU tests' shared steps (these do read denoise_ref)
+def pu_err(got, want, scale=1.0):
+    """(mean, max) |error| in the network-output (PU) domain of two denoised images."""
+    import denoise_ref as ref
+    to_x = lambda y: ref.pu_forward(np.float32(scale) * y) * ref.NORM_SCALE   # noqa: E731
+    e = np.abs(to_x(got) - to_x(want))
+    return float(e.mean()), float(e.max())
+
+
+def run(d, color, albedo, normal, scale=None):
+    """one Denoiser.execute on device copies of the images; the output as a numpy array"""
+    import torch
+    dev = lambda a: torch.from_numpy(a).cuda()   # noqa: E731
+    out = d.execute(dev(color), dev(albedo), dev(normal), input_scale=scale)
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+def check_every_layer(r, d, w, monkeypatch, images, fill):
+    """The per-convolution comparison of tests/test_gpu_denoise.py's docstring on `images` at the input scale 0.9 (benign
+    images there, hostile ones in tests/test_gpu_denoise_inputs.py).  Returns the output and the dumped tensors."""
+    import denoise_ref as ref
+    from restir_amd.denoise import Denoiser
+    color, albedo, normal = images
+    H, W = color.shape[:2]
+    if fill is not None:
+        monkeypatch.setenv("RESTIR_DN_FILL", fill)
+        d = Denoiser(r, w)
+    try:
+        got = run(d, color, albedo, normal, scale=0.9)
+        dumps = [d.dump(i) for i in range(16)]
+    finally:
+        if fill is not None:
+            d.close()
+    t = {}
+    for i, (a, real) in enumerate(dumps):
+        assert not a[0].any() and not a[-1].any() and not a[:, 0].any() and not a[:, -1].any(), f"tensor {i}: border"
+        assert not a[..., real:].any(), f"tensor {i}: channel padding"
+        t[i] = a[1:-1, 1:-1, :real].astype(np.float64).transpose(2, 0, 1)
+    # the network input tensor: the reference's preprocessing rounded to float16
+    want_in = ref.preprocess(color, albedo, normal, np.float32(0.9), 9).astype(np.float16).astype(np.float64)
+    assert np.abs(t[0] - want_in).max() <= np.abs(np.spacing(want_in.astype(np.float16))).max()
+    for name, srcs, post, dst in ref.NET:
+        y = ref.layer64(w, name, [(t[s], up) for s, up in srcs], post)
+        if dst is None:        # dec_conv0 + output transform, float32 on the GPU
+            want = ref.postprocess(y.astype(np.float32), np.float32(0.9), H, W)
+            np.testing.assert_allclose(got, want, rtol=2e-4, atol=1e-6, err_msg=name)
+            continue
+        y16 = y.astype(np.float16)
+        g16 = t[dst].astype(np.float16)
+        assert g16.shape == y16.shape, name
+        ulp = np.spacing(np.abs(y16)).astype(np.float64)
+        mag = ref.layer64(w, name, [(t[s], up) for s, up in srcs], post, magnitude=True)
+        bound = ulp * 1.0001 + 3e-5 * mag
+        diff = np.abs(g16.astype(np.float64) - y16.astype(np.float64))
+        off = diff > 0
+        print(f"{name}: {off.mean() * 100:.3f} % of {diff.size} elements differ, max {float((diff / bound).max()):.3f} of the bound")
+        assert (diff <= bound).all(), (name, float((diff / bound).max()))
+        assert off.mean() <= 0.02, (name, float(off.mean()))
+    return got, dumps

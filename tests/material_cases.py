@@ -12,9 +12,9 @@ MIS and path ground truths, which sample by the eval's rule (rs_mis.h).
                  and which has two emitter materials; EDGES changes one property of those walls or of one emitter
   rough_scene()  scenes.textured_cornell with the Phong block's roughness map replaced (ROUGH_MAPS)
 
-Comparisons.  Frames are sanitised and hold no NaN: np.array_equal.  G-buffers and reservoirs hold what the scene
-gave them -- a NaN shininess, a NaN weight sum -- and a NaN equals nothing, itself included, so `same` is
-np.array_equal with equal_nan=True: every element equal, or NaN on both sides.
+Comparisons (tests/gpu_harness.py assert_same_render).  Frames are sanitised and hold no NaN: np.array_equal.
+G-buffers and reservoirs hold what the scene gave them -- a NaN shininess, a NaN weight sum -- and a NaN equals
+nothing, itself included, so `same` is np.array_equal with equal_nan=True: every element equal, or NaN on both sides.
 """
 from __future__ import annotations
 
@@ -24,13 +24,15 @@ from dataclasses import replace
 
 import numpy as np
 
+import gpu_harness as GH
+from gpu_harness import TYPE_COL, Render, assert_same_render, same  # noqa: F401  (used as M.<name> by the tests)
 from restir_amd import params as P
 from restir_amd import scenes
 from restir_amd.scenes import (DIELECTRIC, DIELECTRIC_TRANSPARENT, LAMBERT, MIRROR, NORMAL, PHONG, UNSUPPORTED,
                                Material)
 
 SIZES = ((64, 48), (50, 38))          # 50 x 38 is no multiple of the 8 x 8 wave tile
-TYPE_COL, IM_COL, SHIN_COL = 17, 18, 15
+IM_COL, SHIN_COL = 18, 15          # G-buffer columns, beside gpu_harness.TYPE_COL
 ALL_TYPES = (NORMAL, LAMBERT, PHONG, MIRROR, DIELECTRIC, DIELECTRIC_TRANSPARENT, UNSUPPORTED)
 MIN_PIXELS = 100
 
@@ -45,10 +47,6 @@ def rotation(classes):
     """type -> the next type of its class (cyclic): every material of a class of more than one member is re-typed,
     none leaves its class"""
     return {t: c[(i + 1) % len(c)] for c in classes for i, t in enumerate(c)}
-
-
-def same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
 
 
 # ---------------------------------------------------------------- rooms
@@ -282,37 +280,10 @@ def write_default_obj(sc, obj_path):
 
 
 # ---------------------------------------------------------------- the oracle's renders, computed once and shared
-class Render:
-    """frames (list of (H, W, 3)), the G-buffer and the reservoirs after the last frame; read-only"""
-
-    def __init__(self, frames, gbuffer, reservoirs):
-        self.frames, self.gbuffer, self.reservoirs = frames, gbuffer, reservoirs
-        for a in (*frames, gbuffer, reservoirs):
-            a.setflags(write=False)
-
-
-def run_restir(renderer, handle, sc, n_frames, frame_fn):
-    """n_frames over the orbit camera on either renderer; frame_fn(handle, camera, f) renders one frame"""
-    renderer.reset_history()
-    frames = [np.array(frame_fn(handle, camera(sc, f), f), copy=True) for f in range(n_frames)]
-    return Render(frames, np.array(renderer.gbuffer(), copy=True), np.array(renderer.reservoirs(), copy=True))
-
-
-def oracle_restir(sc, prm, size, n_frames):
-    import oracle_lib as O
-    o, os_ = O.OracleRenderer(*size), O.OracleScene(sc)
-    return run_restir(o, os_, sc, n_frames, lambda h, c, f: o.render(h, c, prm, f))
-
-
-def gpu_restir(sc, prm, size, n_frames, traversal=None, split=None):
-    from restir_amd.renderer import Renderer
-    g = Renderer(*size)
-    if traversal:
-        g.set_traversal(traversal)
-    if split:
-        g.set_initial_split(split)
-    gs = g.load_scene(sc)
-    return run_restir(g, gs, sc, n_frames, lambda h, c, f: g.produce_restir(h, c, prm, f))
+# tests/gpu_harness.py's runs, on the materials' orbit
+run_restir = functools.partial(GH.run_restir, camera=camera)
+oracle_restir = functools.partial(GH.oracle_restir, camera=camera)
+gpu_restir = functools.partial(GH.gpu_restir, camera=camera)
 
 
 @functools.lru_cache(maxsize=None)
@@ -342,30 +313,6 @@ def oracle_path(sc, size, n_frames=2):
     o, os_ = O.OracleRenderer(*size), O.OracleScene(sc)
     return [PO.render_path(o, os_, sc.camera, P.default_params(), f, PATH_SPP, max_bounces=PATH_BOUNCES)
             for f in range(n_frames)]
-
-
-def _differ(a, b):
-    return ~((a == b) | (np.isnan(a) & np.isnan(b)))
-
-
-def assert_same_render(a, b, what, type_column=True):
-    """frames, G-buffer (without the type column if asked) and reservoirs equal element by element; the message
-    names every part that is not"""
-    bad = []
-    for f, (x, y) in enumerate(zip(a.frames, b.frames)):
-        if not np.array_equal(x, y):
-            bad.append(f"frame {f}: {int(np.any(x != y, -1).sum())} pixels")
-    ga, gb = a.gbuffer, b.gbuffer
-    if not type_column:
-        keep = [c for c in range(ga.shape[-1]) if c != TYPE_COL]
-        ga, gb = ga[..., keep], gb[..., keep]
-    if not same(ga, gb):
-        d = _differ(ga, gb)
-        bad.append(f"G-buffer: columns {sorted(set(np.nonzero(d)[-1].tolist()))} on {int(d.any(-1).sum())} pixels")
-    if not same(a.reservoirs, b.reservoirs):
-        d = _differ(a.reservoirs, b.reservoirs)
-        bad.append(f"reservoirs: columns {sorted(set(np.nonzero(d)[-1].tolist()))} on {int(d.any(-1).sum())} pixels")
-    assert not bad, f"{what}: " + "; ".join(bad)
 
 
 def type_pixels(gbuffer):

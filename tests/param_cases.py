@@ -16,7 +16,8 @@ from __future__ import annotations
 
 import functools
 
-import material_cases as M
+import gpu_harness as GH
+from material_cases import camera  # noqa: F401  (the sweep's frames ride the materials' orbit)
 from restir_amd import params as P
 from restir_amd import scenes
 
@@ -141,7 +142,7 @@ def changed_fields(case):
 @functools.lru_cache(maxsize=None)
 def oracle(case=None, wh=None):
     """the oracle's run of `case` (None: BASE) at its own size, or at wh"""
-    return M.oracle_restir(scene(), params(case), wh or size(case), FRAMES)
+    return GH.oracle_restir(scene(), params(case), wh or size(case), FRAMES, camera)
 
 
 GT_KINDS = ("mis", "path", "unbiased")

@@ -37,13 +37,6 @@ import denoise_ref as ref  # noqa: E402  (oracle/, test infrastructure)
 _images = C.benign_images       # lognormal colour, uniform albedo, unit normals; the hostile ones: test_gpu_denoise_inputs.py
 
 
-def _err(got, want, scale=1.0):
-    """(mean, max) |error| in the network-output (PU) domain of two denoised images."""
-    to_x = lambda y: ref.pu_forward(np.float32(scale) * y) * ref.NORM_SCALE   # noqa: E731
-    e = np.abs(to_x(got) - to_x(want))
-    return float(e.mean()), float(e.max())
-
-
 @pytest.fixture(scope="module")
 def ctx():
     assert torch.cuda.is_available()
@@ -55,23 +48,16 @@ def ctx():
     r.close()
 
 
-def _run(d, color, albedo, normal, scale=None):
-    dev = lambda a: torch.from_numpy(a).cuda()   # noqa: E731
-    out = d.execute(dev(color), dev(albedo), dev(normal), input_scale=scale)
-    torch.cuda.synchronize()
-    return out.cpu().numpy()
-
-
 @pytest.mark.parametrize("H,W", [(48, 64), (29, 37), (1, 1), (16, 16), (135, 240)])
 def test_denoise_matches_reference(ctx, H, W):
     r, d, w = ctx
     color, albedo, normal = _images(H, W, seed=H * 1000 + W)
-    got = _run(d, color, albedo, normal, scale=0.7)
+    got = C.run(d, color, albedo, normal, scale=0.7)
     want_q = ref.denoise(color, albedo, normal, w, input_scale=0.7, quantize=True)
     want = ref.denoise(color, albedo, normal, w, input_scale=0.7)
     assert got.shape == (H, W, 3) and np.isfinite(got).all()
-    mq, xq = _err(got, want_q, 0.7)
-    m32, x32 = _err(got, want, 0.7)
+    mq, xq = C.pu_err(got, want_q, 0.7)
+    m32, x32 = C.pu_err(got, want, 0.7)
     print(f"{H}x{W}: PU-domain |err| vs fp16-storage reference mean {mq:.2e} max {xq:.2e}; vs fp32 {m32:.2e} / {x32:.2e}")
     assert mq <= 1e-3 and xq <= 2e-2, (mq, xq)
 
@@ -83,49 +69,7 @@ def test_every_layer_matches_float64(ctx, monkeypatch, H, W, fill):
     largest n-tile count <= 4 that divides its n-tiles -- k_conv3 with 1, 2, 3 and 4 n-tiles, storing and
     pooling, where the default at these sizes runs nearly every layer with 1."""
     r, d, w = ctx
-    check_every_layer(r, d, w, monkeypatch, _images(H, W, seed=31 + H), fill)
-
-
-def check_every_layer(r, d, w, monkeypatch, images, fill):
-    """The per-convolution comparison of the module docstring on `images` at the input scale 0.9 (shared with
-    tests/test_gpu_denoise_inputs.py, which feeds it hostile images).  Returns the output and the dumped tensors."""
-    color, albedo, normal = images
-    H, W = color.shape[:2]
-    if fill is not None:
-        monkeypatch.setenv("RESTIR_DN_FILL", fill)
-        d = Denoiser(r, w)
-    try:
-        got = _run(d, color, albedo, normal, scale=0.9)
-        dumps = [d.dump(i) for i in range(16)]
-    finally:
-        if fill is not None:
-            d.close()
-    t = {}
-    for i, (a, real) in enumerate(dumps):
-        assert not a[0].any() and not a[-1].any() and not a[:, 0].any() and not a[:, -1].any(), f"tensor {i}: border"
-        assert not a[..., real:].any(), f"tensor {i}: channel padding"
-        t[i] = a[1:-1, 1:-1, :real].astype(np.float64).transpose(2, 0, 1)
-    # the network input tensor: the reference's preprocessing rounded to float16
-    want_in = ref.preprocess(color, albedo, normal, np.float32(0.9), 9).astype(np.float16).astype(np.float64)
-    assert np.abs(t[0] - want_in).max() <= np.abs(np.spacing(want_in.astype(np.float16))).max()
-    for name, srcs, post, dst in ref.NET:
-        y = ref.layer64(w, name, [(t[s], up) for s, up in srcs], post)
-        if dst is None:        # dec_conv0 + output transform, float32 on the GPU
-            want = ref.postprocess(y.astype(np.float32), np.float32(0.9), H, W)
-            np.testing.assert_allclose(got, want, rtol=2e-4, atol=1e-6, err_msg=name)
-            continue
-        y16 = y.astype(np.float16)
-        g16 = t[dst].astype(np.float16)
-        assert g16.shape == y16.shape, name
-        ulp = np.spacing(np.abs(y16)).astype(np.float64)
-        mag = ref.layer64(w, name, [(t[s], up) for s, up in srcs], post, magnitude=True)
-        bound = ulp * 1.0001 + 3e-5 * mag
-        diff = np.abs(g16.astype(np.float64) - y16.astype(np.float64))
-        off = diff > 0
-        print(f"{name}: {off.mean() * 100:.3f} % of {diff.size} elements differ, max {float((diff / bound).max()):.3f} of the bound")
-        assert (diff <= bound).all(), (name, float((diff / bound).max()))
-        assert off.mean() <= 0.02, (name, float(off.mean()))
-    return got, dumps
+    C.check_every_layer(r, d, w, monkeypatch, _images(H, W, seed=31 + H), fill)
 
 
 def test_channel_split_bit_identical(ctx, monkeypatch):
@@ -135,12 +79,12 @@ def test_channel_split_bit_identical(ctx, monkeypatch):
     r, d, w = ctx
     H, W = 37, 83
     color, albedo, normal = _images(H, W, seed=13)
-    o0 = _run(d, color, albedo, normal, scale=0.8)
+    o0 = C.run(d, color, albedo, normal, scale=0.8)
     t0 = [d.dump(i)[0] for i in range(16)]
     monkeypatch.setenv("RESTIR_DN_FILL", "1")
     d1 = Denoiser(r, w)
     try:
-        o1 = _run(d1, color, albedo, normal, scale=0.8)
+        o1 = C.run(d1, color, albedo, normal, scale=0.8)
         t1 = [d1.dump(i)[0] for i in range(16)]
     finally:
         d1.close()
@@ -164,7 +108,7 @@ def test_pipelined_conv_bit_identical(monkeypatch, H, W, grid):
             if grid is not None:
                 monkeypatch.setenv("RESTIR_DN_PIPE_GRID", grid)
             d = Denoiser(r, w)
-            out = _run(d, color, albedo, normal, scale=0.8)
+            out = C.run(d, color, albedo, normal, scale=0.8)
             outs[pipe] = (out, [d.dump(i)[0] for i in range(16)])
             d.close()
     finally:
@@ -179,7 +123,7 @@ def test_autoexposure_matches_reference(ctx):
     r, d, w = ctx
     for (H, W), seed in (((48, 64), 1), ((37, 91), 2), ((1080 // 4, 1920 // 4), 3)):
         color, albedo, normal = _images(H, W, seed)
-        _run(d, color, albedo, normal)                    # input_scale unset: auto-exposure
+        C.run(d, color, albedo, normal)                    # input_scale unset: auto-exposure
         got = d.scale()
         want = float(ref.autoexposure(color))
         assert got == pytest.approx(want, rel=1e-4), (H, W, got, want)
@@ -188,9 +132,9 @@ def test_autoexposure_matches_reference(ctx):
 def test_autoexposure_end_to_end(ctx):
     r, d, w = ctx
     color, albedo, normal = _images(40, 56, seed=5)
-    got = _run(d, color, albedo, normal)
+    got = C.run(d, color, albedo, normal)
     want = ref.denoise(color, albedo, normal, w, quantize=True)
-    m, x = _err(got, want, ref.autoexposure(color))
+    m, x = C.pu_err(got, want, ref.autoexposure(color))
     assert m <= 1e-3 and x <= 2e-2, (m, x)
 
 
@@ -200,8 +144,8 @@ def test_half_archive_equals_float_archive(ctx):
     d_f = Denoiser(r, tza.write_tza(wh, "f"))
     d_h = Denoiser(r, tza.write_tza(wh, "h"))
     color, albedo, normal = _images(32, 48, seed=9)
-    a = _run(d_f, color, albedo, normal, scale=1.0)
-    b = _run(d_h, color, albedo, normal, scale=1.0)
+    a = C.run(d_f, color, albedo, normal, scale=1.0)
+    b = C.run(d_h, color, albedo, normal, scale=1.0)
     np.testing.assert_array_equal(a, b)
     d_f.close()
     d_h.close()
@@ -217,7 +161,7 @@ def test_color_only_and_albedo_weights(ctx):
         out = d.execute(dev(color), dev(albedo) if ic >= 6 else None, None, input_scale=1.3)
         torch.cuda.synchronize()
         want = ref.denoise(color, albedo, normal, w, input_scale=1.3, quantize=True)
-        m, x = _err(out.cpu().numpy(), want, 1.3)
+        m, x = C.pu_err(out.cpu().numpy(), want, 1.3)
         assert m <= 1e-3 and x <= 2e-2, (ic, m, x)
         d.close()
 
@@ -238,7 +182,7 @@ def test_denoise_frame_and_post_display():
     g = r.gbuffer()                                      # per pixel: pos3 n3 kd3 ks3 Le3 ...
     normal, kd = g[..., 3:6], g[..., 6:9]
     want = ref.denoise(frame, kd, normal, w, quantize=True)
-    m, x = _err(got, want, ref.autoexposure(frame))
+    m, x = C.pu_err(got, want, ref.autoexposure(frame))
     assert m <= 1e-3 and x <= 2e-2, (m, x)
     # post_frame(denoise=True): display = compress(aces(denoised))
     r.post_reset()

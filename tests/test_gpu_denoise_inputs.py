@@ -30,7 +30,7 @@ from restir_amd.renderer import RS_E_INVALID, RS_E_UNSUPPORTED, RS_OK  # noqa: E
 
 import denoise_cases as C  # noqa: E402
 import denoise_ref as ref  # noqa: E402  (oracle/, test infrastructure)
-from test_gpu_denoise import _err, _run, check_every_layer  # noqa: E402
+from gpu_harness import bits  # noqa: E402
 
 
 @pytest.fixture(scope="module")
@@ -44,13 +44,9 @@ def ctx():
     r.close()
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint16 if a.dtype == np.float16 else np.uint32)
-
-
 def _run_all(d, images, scale=None):
     """(output, scale, the 16 dumped tensors with their borders and channel padding) of one execute."""
-    out = _run(d, *images, scale=scale)
+    out = C.run(d, *images, scale=scale)
     return out, np.float32(d.scale()), [d.dump(i)[0] for i in range(16)]
 
 
@@ -58,8 +54,8 @@ def _assert_same(a, b, what):
     (oa, sa, ta), (ob, sb, tb) = a, b
     assert sa.tobytes() == sb.tobytes(), (what, sa, sb)
     for i in range(16):
-        assert ta[i].shape == tb[i].shape and np.array_equal(_bits(ta[i]), _bits(tb[i])), f"{what}: tensor {i}"
-    assert np.array_equal(_bits(oa), _bits(ob)), f"{what}: output"
+        assert ta[i].shape == tb[i].shape and np.array_equal(bits(ta[i]), bits(tb[i])), f"{what}: tensor {i}"
+    assert np.array_equal(bits(oa), bits(ob)), f"{what}: output"
 
 
 def _class_image(cls, H, W):
@@ -76,7 +72,7 @@ def test_scale_matches_definition(ctx, H, W, cls):
     r, d, w = ctx
     images = _class_image(cls, H, W)
     want = C.autoexposure64(images[0])
-    _run(d, *images)                                       # input_scale unset: auto-exposure
+    C.run(d, *images)                                       # input_scale unset: auto-exposure
     got = d.scale()
     print(f"{H}x{W} {cls}: scale {got!r}, float64 definition {want!r}, rel {abs(got - want) / want:.2e}")
     if cls == "black":
@@ -108,7 +104,7 @@ def test_network_input(ctx, H, W):
     r, d, w = ctx
     scale = 0.8
     color, albedo, normal = C.hostile_images(H, W, seed=7 * H, scale=scale)
-    _run(d, color, albedo, normal, scale=scale)
+    C.run(d, color, albedo, normal, scale=scale)
     a, real = d.dump(0)
     Hp, Wp = -(-H // 16) * 16, -(-W // 16) * 16
     assert a.shape == (Hp + 2, Wp + 2, 16) and real == 9
@@ -152,7 +148,7 @@ def test_every_layer_matches_float64_hostile(ctx, monkeypatch, H, W, fill):
     """test_gpu_denoise.py's per-convolution bound (1 float16 ulp + 3e-5 x magnitude, at most 2 % of the elements
     different) on hostile portrait images."""
     r, d, w = ctx
-    got, dumps = check_every_layer(r, d, w, monkeypatch, C.hostile_images(H, W, seed=31 + H, scale=0.9), fill)
+    got, dumps = C.check_every_layer(r, d, w, monkeypatch, C.hostile_images(H, W, seed=31 + H, scale=0.9), fill)
     for i, (a, real) in enumerate(dumps):
         assert np.isfinite(a).all(), f"tensor {i}"
     assert np.isfinite(got).all() and (got >= 0).all()
@@ -165,9 +161,9 @@ def test_end_to_end_hostile(ctx):
     with np.errstate(all="ignore"):
         want = ref.denoise(color, albedo, normal, w, quantize=True)
         s = ref.autoexposure(color)
-    got = _run(d, color, albedo, normal)
+    got = C.run(d, color, albedo, normal)
     assert np.isfinite(got).all() and (got >= 0).all() and got.max() > 0
-    m, x = _err(got, want, s)
+    m, x = C.pu_err(got, want, s)
     print(f"hostile 47x33, auto-exposure {float(s):.3e}: PU-domain |err| mean {m:.2e} max {x:.2e}")
     assert m <= 1e-3 and x <= 2e-2, (m, x)
 
@@ -236,7 +232,7 @@ def test_loud_errors_leave_the_denoiser_working(ctx):
     images = C.benign_images(16, 16, seed=4)
     before = _run_all(d, images, 0.8)
     want = ref.denoise(*images, w, input_scale=0.8, quantize=True)
-    m, x = _err(before[0], want, 0.8)
+    m, x = C.pu_err(before[0], want, 0.8)
     assert m <= 1e-3 and x <= 2e-2, (m, x)
 
     dev = [torch.from_numpy(a).cuda() for a in images]

@@ -29,29 +29,21 @@ import numpy as np
 import pytest
 
 import bvh_brute as B
+from gpu_harness import bits, set_env
 from restir_amd.renderer import Renderer
 
 pytestmark = pytest.mark.gpu
 
 AMBIGUOUS_CAP = 0.02        # a condition on the inputs, not a tolerance on the result
-TREES = {"ploc_wide": (None, None), "ploc_skip": (None, "off"), "lbvh_wide": ("lbvh", None), "lbvh_skip": ("lbvh", "off")}
 # classes whose 8-wide tree must be live when it is not switched off.  The soup at 1e20 and the 300 coincident
 # triangles over the grid load as RS_WIDE_TOO_DEEP today (no collapse within the walk's 8 levels): their per-lane walks
 # take the skip pointers, with the same answers -- a fallback that costs speed only, so it is reported, not required
 WIDE_LIVE = set(B.CLASS_NAMES) - {"huge", "dups"}
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def _setenv(monkeypatch, tree):
-    bvh, wide = TREES[tree]
-    for k, v in (("RESTIR_BVH", bvh), ("RESTIR_WIDE", wide)):
-        if v is None:
-            monkeypatch.delenv(k, raising=False)
-        else:
-            monkeypatch.setenv(k, v)
+    bvh, wide = B.TREES[tree]
+    set_env(monkeypatch, RESTIR_BVH=bvh, RESTIR_WIDE=wide)
     return bvh, wide
 
 
@@ -103,11 +95,11 @@ def _assert_lbvh_differs(monkeypatch, g, sc, nodes, n_tris):
     monkeypatch.setenv("RESTIR_BVH", "lbvh")
     rn, _ = ref.bvh_tree()
     ref.close()
-    assert rn.shape != nodes.shape or not np.array_equal(_bits(rn), _bits(nodes)), "RESTIR_BVH=lbvh built the default tree"
+    assert rn.shape != nodes.shape or not np.array_equal(bits(rn), bits(nodes)), "RESTIR_BVH=lbvh built the default tree"
 
 
 @pytest.mark.parametrize("name", B.CLASS_NAMES)
-@pytest.mark.parametrize("tree", list(TREES))
+@pytest.mark.parametrize("tree", list(B.TREES))
 def test_hostile_class(tree, name, monkeypatch):
     cls, (o, d, tb, pb), (ao, ad, atn, atf, skip, aref) = _reference(name)
     share = float(skip.mean())
@@ -124,17 +116,17 @@ def test_hostile_class(tree, name, monkeypatch):
         _assert_lbvh_differs(monkeypatch, g, sc, nodes, cls.n_tris)
     # determinism: a second build, and a rebuild under the same variables, give the same words
     n2, p2 = gs2.bvh_tree()
-    assert gs2.n_nodes == gs.n_nodes and np.array_equal(_bits(n2), _bits(nodes)) and np.array_equal(p2, prims)
+    assert gs2.n_nodes == gs.n_nodes and np.array_equal(bits(n2), bits(nodes)) and np.array_equal(p2, prims)
     gs2.rebuild()
     n2, p2 = gs2.bvh_tree()
-    assert gs2.n_nodes == gs.n_nodes and np.array_equal(_bits(n2), _bits(nodes)) and np.array_equal(p2, prims)
+    assert gs2.n_nodes == gs.n_nodes and np.array_equal(bits(n2), bits(nodes)) and np.array_equal(p2, prims)
     assert gs2.walk_info() == info
     gs2.close()
     print(f"[hostile] {name} on {tree}: {stats}, wide {info['status']}, closest hits {100 * (pb >= 0).mean():.1f} %, "
           f"occluded {100 * aref.mean():.1f} %, excluded {100 * share:.2f} %")
     for lockstep in (True, False):
         t, prim = g.debug_trace(gs, o, d, float(cls.tnear), 3.0e38, any_hit=False, lockstep=lockstep)
-        bad = np.flatnonzero((prim != pb) | (_bits(t) != _bits(tb)))
+        bad = np.flatnonzero((prim != pb) | (bits(t) != bits(tb)))
         assert bad.size == 0, (f"{name} on {tree}, lockstep={lockstep}: {bad.size} of {len(o)} closest rays differ from "
                                f"brute force, first {bad[:5]}: prim {prim[bad[:5]]} vs {pb[bad[:5]]}")
         if hasattr(cls, "never_hit"):
@@ -147,7 +139,7 @@ def test_hostile_class(tree, name, monkeypatch):
     g.close()
 
 
-@pytest.mark.parametrize("tree", list(TREES))
+@pytest.mark.parametrize("tree", list(B.TREES))
 def test_size_ladder(tree, monkeypatch):
     """Soups of 1 .. 4097 triangles: around the leaf maximum (8, 9), PLOC's search radius (16, 17, 18, 33) and block
     (255, 256, 257, 512, 513) and beyond.  For n <= 3 without a wide tree the status is whatever rs_scene_walk_info
@@ -164,7 +156,7 @@ def test_size_ladder(tree, monkeypatch):
             _assert_lbvh_differs(monkeypatch, g, sc, nodes, n)
         for lockstep in (True, False):
             t, prim = g.debug_trace(gs, o, d, float(cls.tnear), 3.0e38, any_hit=False, lockstep=lockstep)
-            bad = np.flatnonzero((prim != pb) | (_bits(t) != _bits(tb)))
+            bad = np.flatnonzero((prim != pb) | (bits(t) != bits(tb)))
             assert bad.size == 0, f"n={n} on {tree}, lockstep={lockstep}: {bad.size} closest rays differ, first {bad[:5]}"
         gs.close()
     g.close()

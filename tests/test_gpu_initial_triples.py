@@ -16,17 +16,13 @@ is off, and both are asserted after every frame, as tests/test_gpu_light_lds.py 
 A renderer per (shape, scene, walk kind, table source) is made once and renders every candidate count: no pass here
 keeps history between frames, and the switch is read when a context is created.
 """
-import os
-
-import numpy as np
 import pytest
 
+import gpu_harness as GH
 import oracle_lib as O
 from restir_amd import params as P
 from restir_amd import scenes
 from restir_amd.distributed import GpuTileBackend
-from restir_amd.renderer import Renderer
-from test_gpu_lockstep_walks import _c2_blocker
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +38,7 @@ class _World:
 
     def __init__(self):
         self.made = {"many_lights": lambda: scenes.cornell_many_lights(64), "box": lambda: scenes.cornell_box(8),
-                     "blocker": _c2_blocker}
+                     "blocker": lambda: GH.with_ceiling_blocker(scenes.cornell_many_lights(1024), "c2_blocker")}
         self.sc, self.osc, self.gpu, self.orc = {}, {}, {}, {}
 
     def scene(self, which):
@@ -54,17 +50,9 @@ class _World:
     def renderer(self, which, W, H, walk, lds):
         key = (which, W, H, walk, lds)
         if key not in self.gpu:
-            old = os.environ.get("RESTIR_LIGHT_LDS")
-            os.environ["RESTIR_LIGHT_LDS"] = lds
-            try:
-                g = Renderer(W, H)
-            finally:
-                if old is None:
-                    del os.environ["RESTIR_LIGHT_LDS"]
-                else:
-                    os.environ["RESTIR_LIGHT_LDS"] = old
-            g.set_traversal(walk)
-            g.set_initial_split("off")
+            with pytest.MonkeyPatch.context() as mp:
+                GH.set_env(mp, RESTIR_LIGHT_LDS=lds)
+                g = GH.pinned_renderer(W, H, walk)
             self.gpu[key] = (g, g.load_scene(self.scene(which)[0]))
         return self.gpu[key]
 
@@ -86,30 +74,20 @@ def world():
     w.close()
 
 
-def _cam(sc):
-    return scenes.orbit_camera(sc.camera, FRAME, 48, 0.2)
-
-
 def _gpu(world, which, W, H, prm, walk, lds="auto"):
     """(frame, reservoirs, rays) of one frame with the walks pinned to `walk`"""
     g, gs = world.renderer(which, W, H, walk, lds)
-    frame = g.produce_restir(gs, _cam(world.scene(which)[0]), prm, FRAME).copy()
+    frame = g.produce_restir(gs, GH.orbit_cam(world.scene(which)[0], FRAME), prm, FRAME).copy()
     rays = int(g.last_times.rays)
-    assert g.initial_split()[1] is False, "the frame's initial pass ran candidate-split"
-    assert g.traversal()[1] == (0 if walk == "lockstep" else 1), "the frame did not walk as pinned"
+    GH.assert_walked(g, walk)
     return frame, g.reservoirs().copy(), rays
 
 
 def _oracle(world, which, W, H, prm):
     sc, osc = world.scene(which)
     o = world.oracle(W, H)
-    frame = o.render(osc, _cam(sc), prm, FRAME)
+    frame = o.render(osc, GH.orbit_cam(sc, FRAME), prm, FRAME)
     return frame, o.reservoirs(), o.rays
-
-
-def _same(a, b, what):
-    assert np.isfinite(a).all(), what
-    assert np.array_equal(a, b), f"{what}: {int(np.any(a != b, -1).sum())} px differ"
 
 
 def _check(world, which, W, H, prm, what, tables=("auto", "off")):
@@ -118,10 +96,10 @@ def _check(world, which, W, H, prm, what, tables=("auto", "off")):
     for lds in tables:
         fa, ra, na = _gpu(world, which, W, H, prm, "lockstep", lds)
         w = f"{what}, RESTIR_LIGHT_LDS={lds}"
-        _same(fa, fb, f"{w}: frame, lockstep vs per-lane")
-        _same(fa, fo, f"{w}: frame, lockstep vs oracle")
-        _same(ra, rb, f"{w}: reservoirs, lockstep vs per-lane")
-        _same(ra, ro, f"{w}: reservoirs, lockstep vs oracle")
+        GH.assert_equal_finite(fa, fb, f"{w}: frame, lockstep vs per-lane")
+        GH.assert_equal_finite(fa, fo, f"{w}: frame, lockstep vs oracle")
+        GH.assert_equal_finite(ra, rb, f"{w}: reservoirs, lockstep vs per-lane")
+        GH.assert_equal_finite(ra, ro, f"{w}: reservoirs, lockstep vs oracle")
         assert na == nb and na > 0, f"{w}: {na} rays in lockstep, {nb} per lane"
 
 
@@ -161,16 +139,15 @@ def test_band(world, m_area, m_brdf):
     for walk in ("lockstep", "lane"):
         g, gs = world.renderer("many_lights", W, H, walk, "auto")
         be = GpuTileBackend(g)
-        be.begin(gs, _cam(sc), prm, FRAME, y0, y1, 0, 0)
+        be.begin(gs, GH.orbit_cam(sc, FRAME), prm, FRAME, y0, y1, 0, 0)
         be.temporal()
         band = be.finish(timed=True).cpu().numpy().reshape(-1, W, 3).copy()
-        assert g.initial_split()[1] is False, "the band's initial pass ran candidate-split"
-        assert g.traversal()[1] == (0 if walk == "lockstep" else 1), "the band did not walk as pinned"
+        GH.assert_walked(g, walk)
         out[walk] = band, g.reservoirs()[y0:y1].copy(), int(g.last_times.rays)
     fo, ro, _ = _oracle(world, "many_lights", W, H, prm)
     what = f"band ({m_area}, {m_brdf})"
-    _same(out["lockstep"][0], out["lane"][0], f"{what}: rows, lockstep vs per-lane")
-    _same(out["lockstep"][0], fo[y0:y1], f"{what}: rows, lockstep vs oracle")
-    _same(out["lockstep"][1], out["lane"][1], f"{what}: reservoirs, lockstep vs per-lane")
-    _same(out["lockstep"][1], ro[y0:y1], f"{what}: reservoirs, lockstep vs oracle")
+    GH.assert_equal_finite(out["lockstep"][0], out["lane"][0], f"{what}: rows, lockstep vs per-lane")
+    GH.assert_equal_finite(out["lockstep"][0], fo[y0:y1], f"{what}: rows, lockstep vs oracle")
+    GH.assert_equal_finite(out["lockstep"][1], out["lane"][1], f"{what}: reservoirs, lockstep vs per-lane")
+    GH.assert_equal_finite(out["lockstep"][1], ro[y0:y1], f"{what}: reservoirs, lockstep vs oracle")
     assert out["lockstep"][2] == out["lane"][2] and out["lockstep"][2] > 0, f"{what}: rays {out['lockstep'][2]} vs {out['lane'][2]}"

@@ -18,26 +18,26 @@ import pytest
 import bvh_brute as B
 from restir_amd import params as P
 from restir_amd import scenes
-from restir_amd.renderer import Renderer
 
-import test_gpu_skip_walks as S
-from test_gpu_skip_walks import oracle_frames, scns  # noqa: F401  (module-scoped fixtures)
+import gpu_harness as GH
+import skip_walk_cases as S
+from skip_walk_cases import oracle_frames, scns  # noqa: F401  (module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
 
 WIDE = {"wide": None, "skip": "off"}
 
 
-@pytest.mark.parametrize("walk", S.WALKS)
+@pytest.mark.parametrize("walk", GH.WALKS)
 @pytest.mark.parametrize("wide", list(WIDE))
 @pytest.mark.parametrize("which", ["c2", "c3"])
 def test_lbvh_frames_equal_default_builder_and_oracle(scns, oracle_frames, which, wide, walk, monkeypatch):  # noqa: F811
     sc, (W, H) = scns[which], S.SIZE[which]
-    prms = S._base_prms()
-    lb = S._sequence(monkeypatch, sc, W, H, walk, WIDE[wide], prms, bvh="lbvh")
-    ref = S._sequence(monkeypatch, sc, W, H, walk, None, prms)
-    S._same_runs(lb, ref, f"lbvh {which} {wide} {walk}")
-    for f, (a, b) in enumerate(zip(lb["frames"], oracle_frames[which])):
+    prms = S.base_prms()
+    lb = S.sequence(monkeypatch, sc, W, H, walk, WIDE[wide], prms, bvh="lbvh")
+    ref = S.sequence(monkeypatch, sc, W, H, walk, None, prms)
+    S.same_runs(lb, ref, f"lbvh {which} {wide} {walk}")
+    for f, (a, b) in enumerate(zip(lb.frames, oracle_frames[which])):
         assert np.array_equal(a, b), f"lbvh {which} {wide} {walk} frame {f}: {int((a != b).any(-1).sum())} px differ from the oracle"
 
 
@@ -46,10 +46,8 @@ def test_lbvh_frames_equal_default_builder_and_oracle(scns, oracle_frames, which
 def test_lbvh_update_refit_rebuild(scns, which, wide, monkeypatch):  # noqa: F811
     sc, (W, H) = scns[which], S.SIZE[which]
     prm = P.c3_params(m_area=8)
-    g, gs = S._load(monkeypatch, W, H, sc, "lane", WIDE[wide], bvh="lbvh")      # (asserts an LBVH was built)
-    f_ = Renderer(W, H)
-    f_.set_traversal("lane")
-    f_.set_initial_split("off")
+    g, gs = S.load(monkeypatch, W, H, sc, "lane", WIDE[wide], bvh="lbvh")      # (asserts an LBVH was built)
+    f_ = GH.pinned_renderer(W, H, "lane")
     n0, p0 = gs.bvh_tree()
     status = gs.walk_info()["status"]
     plan = [(0, 0.05, False), (40, 0.05, True), (90, 0.4, False), (130, 0.4, True)]
@@ -69,7 +67,7 @@ def test_lbvh_update_refit_rebuild(scns, which, wide, monkeypatch):  # noqa: F81
             assert np.array_equal(nodes.view(np.uint32), fn.view(np.uint32)) and np.array_equal(prims, fp)
         cam = scenes.orbit_camera(sc.camera, f, 240, 0.3)
         a = g.produce_restir(gs, cam, prm, f).copy()
-        S._assert_walked(g, "lane")
+        GH.assert_walked(g, "lane")
         b = f_.produce_restir(fresh, cam, prm, f).copy()
         assert np.array_equal(a, b), f"frame {f}: refit != fresh ({int((a != b).any(-1).sum())} px)"
         fresh.close()

@@ -5,58 +5,33 @@ The LDS copy holds the same CDF and guide values and light_index makes the same 
 frame and every reservoir must be bit-identical: the comparisons below are on the raw 32-bit words.  The switch is
 read when a context is created, so every renderer is made after the environment is set.  The walks are pinned to
 lockstep: AUTO's first frames alternate the walk kind to time it, and per-lane frames take the sorted pass, which
-keeps the global tables.  The candidate-split pass is switched off for the same reason (_pin), and every renderer
+keeps the global tables.  The candidate-split pass is switched off for the same reason (_pinned), and every renderer
 asserts after its frames that the one-thread-per-pixel lockstep kernel is what ran.
 """
 import numpy as np
 import pytest
 
+import gpu_harness as GH
 import oracle_lib as O
 from restir_amd import params as P
 from restir_amd import scenes
-from restir_amd.renderer import Renderer
 
 pytestmark = pytest.mark.gpu
 
-PIX_TOL, PIX_FRAC, MEAN_TOL = 1e-4, 0.995, 1e-4      # tests/test_gpu_parity.py test_frame_c2_metric_point's bound
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _assert_same(a, b, what):
-    d = _bits(a) != _bits(b)
-    assert not d.any(), f"{what}: {int(d.reshape(d.shape[0], d.shape[1], -1).any(-1).sum())} px differ"
-
-
-def _assert_close(gpu, ref, what):
-    assert np.isfinite(gpu).all(), what
-    rel = np.linalg.norm(gpu.astype(np.float64) - ref, axis=-1) / np.maximum(np.linalg.norm(ref.astype(np.float64), axis=-1), 1e-3)
-    frac, mean = float((rel <= PIX_TOL).mean()), float(rel.mean())
-    assert frac >= PIX_FRAC and mean <= MEAN_TOL, f"{what}: frac_ok={frac:.5f} mean_rel={mean:.3g} max_rel={rel.max():.3g}"
-
-
-def _pin(g):
-    """The launch the variant belongs to: lockstep walks, and the candidate-split pass off -- AUTO runs these small
-    frames (less than one round of the device's waves) through k_gbuffer_initial_split, which keeps the global tables."""
-    g.set_traversal("lockstep")
-    g.set_initial_split("off")
-
-
-def _assert_one_thread_per_pixel(g):
-    assert g.initial_split()[1] is False, "the last frame's initial pass ran candidate-split: the LDS kernel was not launched"
-    assert g.traversal()[1] == 0, "the last frame did not walk in lockstep"       # TRAV_LOCKSTEP
+def _pinned(monkeypatch, mode, W, H, **kw):
+    """A renderer created under RESTIR_LIGHT_LDS=mode for the launch the variant belongs to: lockstep walks, and the
+    candidate-split pass off -- AUTO runs these small frames (less than one round of the device's waves) through
+    k_gbuffer_initial_split, which keeps the global tables."""
+    GH.set_env(monkeypatch, RESTIR_LIGHT_LDS=mode)
+    return GH.pinned_renderer(W, H, "lockstep", **kw)
 
 
 def _render(monkeypatch, mode, sc, W, H, prm, frames=1):
     """(frames, reservoirs after the last frame, emissive triangles) of a renderer created under RESTIR_LIGHT_LDS=mode"""
-    monkeypatch.setenv("RESTIR_LIGHT_LDS", mode)
-    g = Renderer(W, H)
-    _pin(g)
+    g = _pinned(monkeypatch, mode, W, H)
     gs = g.load_scene(sc)
     out = [g.produce_restir(gs, sc.camera, prm, f).copy() for f in range(frames)]
-    _assert_one_thread_per_pixel(g)
+    GH.assert_walked(g, "lockstep")      # else the LDS kernel was not launched
     res = g.reservoirs()
     n = gs.n_emissive
     gs.close()
@@ -68,8 +43,8 @@ def _off_vs_auto(monkeypatch, sc, W, H, prm, what, frames=1):
     a, ra, n = _render(monkeypatch, "off", sc, W, H, prm, frames)
     b, rb, _ = _render(monkeypatch, "auto", sc, W, H, prm, frames)
     for f in range(frames):
-        _assert_same(a[f], b[f], f"{what} frame {f}")
-    _assert_same(ra, rb, f"{what} reservoirs")
+        GH.assert_same_bits(a[f], b[f], f"{what} frame {f}")
+    GH.assert_same_bits(ra, rb, f"{what} reservoirs")
     return b, n
 
 
@@ -92,7 +67,7 @@ def test_table_full_to_capacity(monkeypatch, which):
     frames, n = _off_vs_auto(monkeypatch, sc, 64, 64, prm, which)
     assert n == 2048
     ref = O.OracleRenderer(64, 64).render(O.OracleScene(sc), sc.camera, prm, 0)
-    _assert_close(frames[0], ref, f"{which} vs oracle")
+    GH.assert_close(frames[0], ref, f"{which} vs oracle")
 
 
 def test_just_over_capacity(monkeypatch):
@@ -134,25 +109,21 @@ def test_moving_lights_run_ahead(monkeypatch):
     from restir_amd.distributed import _CudaBuf
     W, H, n_frames = 64, 64, 4
     sc, prm = scenes.cornell_many_lights(256), P.c3_params(m_area=8)
-    cam = lambda f: scenes.orbit_camera(sc.camera, f, 48, 0.2)
     torch.cuda.set_stream(torch.cuda.Stream())       # the clones below are ordered on the frames' stream
     st = torch.cuda.current_stream().cuda_stream
     out = {}
     for mode in ("off", "auto"):
-        monkeypatch.setenv("RESTIR_LIGHT_LDS", mode)
-        g = Renderer(W, H, stream=st)
-        _pin(g)
-        g.set_run_ahead(2)
+        g = _pinned(monkeypatch, mode, W, H, run_ahead=2, stream=st)
         gs = g.load_scene(sc)
         frames = []
         for f in range(n_frames):
             gs.update_positions(scenes.moving_light_positions(sc, f, 48))
-            g.produce_restir(gs, cam(f), prm, f, copy_out=False, timed=False)
+            g.produce_restir(gs, GH.orbit_cam(sc, f), prm, f, copy_out=False, timed=False)
             frames.append(torch.as_tensor(_CudaBuf(g.frame_device_ptr(), W * H * 12, "<f4", 4), device="cuda").clone())
-        _assert_one_thread_per_pixel(g)
+        GH.assert_walked(g, "lockstep")      # else the LDS kernel was not launched
         out[mode] = [t.cpu().numpy().reshape(H, W, 3) for t in frames], g.reservoirs()
         gs.close()
         g.close()
     for f in range(n_frames):
-        _assert_same(out["off"][0][f], out["auto"][0][f], f"moving lights frame {f}")
-    _assert_same(out["off"][1], out["auto"][1], "moving lights reservoirs")
+        GH.assert_same_bits(out["off"][0][f], out["auto"][0][f], f"moving lights frame {f}")
+    GH.assert_same_bits(out["off"][1], out["auto"][1], "moving lights reservoirs")

@@ -16,10 +16,10 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_harness import assert_close, assert_same_bits, bits
 from restir_amd import params as P
 from restir_amd import scenes
 from restir_amd.renderer import Renderer
-from test_gpu_parity import _assert_close
 
 pytestmark = pytest.mark.gpu
 
@@ -72,17 +72,6 @@ def _scene(name):
     return SCENES[name]()
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(a, b, what):
-    a, b = _bits(a), _bits(b)
-    assert a.shape == b.shape, what
-    bad = np.flatnonzero((a != b).reshape(a.shape[0], -1).any(axis=1)) if a.size else []
-    assert len(bad) == 0, f"{what}: {len(bad)} of {a.shape[0]} differ, first at {bad[:4]}"
-
-
 def _assert_tables(gs, sc, what):
     """The scene's current tables against the oracle's for `sc` (the inputs the tables were built from)."""
     em, cdf, guide = gs.debug_light_tables()
@@ -93,30 +82,30 @@ def _assert_tables(gs, sc, what):
     assert os_.n_emissive == ne
     o_cdf, o_pick, o_area = os_.cdf()
     assert (o_area > 0).all() and (np.diff(o_cdf) > 0).all(), what      # what the scenes here promise
-    _same(cdf, o_cdf, f"{what}: cdf")
-    _same(em[:, 4, 3], o_pick, f"{what}: pick")
-    _same(em[:, 6, 0], o_area, f"{what}: area")
+    assert_same_bits(cdf, o_cdf, f"{what}: cdf")
+    assert_same_bits(em[:, 4, 3], o_pick, f"{what}: pick")
+    assert_same_bits(em[:, 6, 0], o_area, f"{what}: area")
     # the remaining fields, in float32 like the reference
     total = np.cumsum(o_area, dtype=np.float32)[-1]
     inv_area = np.float32(1.0) / o_area
     pdf_brdf = (o_area / total) * inv_area
     pos, nrm = (np.ascontiguousarray(a, np.float32).reshape(-1, 3, 3)[emis] for a in (sc.positions, sc.normals))
-    nb = _bits(nrm)
+    nb = bits(nrm)
     flat = (nb[:, 0] == nb[:, 1]).all(axis=1) & (nb[:, 0] == nb[:, 2]).all(axis=1)
     pdf_area = o_pick * inv_area
-    _same(em[:, 6, 1], inv_area, f"{what}: inv_area")
-    _same(em[:, 0, 3], np.where(flat, pdf_area, -pdf_area), f"{what}: signed pdf_area")
-    _same(em[:, 5, 3], pdf_brdf, f"{what}: pdf_brdf")
+    assert_same_bits(em[:, 6, 1], inv_area, f"{what}: inv_area")
+    assert_same_bits(em[:, 0, 3], np.where(flat, pdf_area, -pdf_area), f"{what}: signed pdf_area")
+    assert_same_bits(em[:, 5, 3], pdf_brdf, f"{what}: pdf_brdf")
     j = np.arange(K_CDF_GUIDE + 1, dtype=np.float32) / np.float32(K_CDF_GUIDE)
     assert np.array_equal(guide, np.searchsorted(cdf, j, "left")), f"{what}: guide"
     # the inputs, carried over
     le = sc.material_arrays()[0][:, 6:9][np.asarray(sc.tri_material)[emis]]
-    _same(em[:, 0:3, 0:3], pos, f"{what}: positions")
-    _same(em[:, 1:4, 3], nrm[:, 0], f"{what}: n0")
-    _same(em[:, 4, 0:3], nrm[:, 1], f"{what}: n1")
-    _same(em[:, 5, 0:3], nrm[:, 2], f"{what}: n2")
-    _same(em[:, 3, 0:3], le, f"{what}: emission")
-    assert not _bits(em[:, 6, 2:]).any() and not _bits(em[:, 7]).any(), f"{what}: padding"
+    assert_same_bits(em[:, 0:3, 0:3], pos, f"{what}: positions")
+    assert_same_bits(em[:, 1:4, 3], nrm[:, 0], f"{what}: n0")
+    assert_same_bits(em[:, 4, 0:3], nrm[:, 1], f"{what}: n1")
+    assert_same_bits(em[:, 5, 0:3], nrm[:, 2], f"{what}: n2")
+    assert_same_bits(em[:, 3, 0:3], le, f"{what}: emission")
+    assert not bits(em[:, 6, 2:]).any() and not bits(em[:, 7]).any(), f"{what}: padding"
     return flat
 
 
@@ -179,6 +168,6 @@ def test_frame_of_chunked_table_matches_oracle():
     gs = g.load_scene(sc)
     a = g.produce_restir(gs, sc.camera, prm, 0).copy()
     b = O.OracleRenderer(W, H).render(O.OracleScene(sc), sc.camera, prm, 0)
-    _assert_close(a, b, "8198 emitters")
+    assert_close(a, b, "8198 emitters")
     gs.close()
     g.close()

@@ -10,13 +10,12 @@ ray ends in its first leaf), and with 0.2 m lights, where the BRDF candidate's r
 direction rarely lands on a 0.02 m quad).  The walk kind is pinned and the candidate-split pass switched off, and both
 are asserted after the frames, as tests/test_gpu_light_lds.py does.
 """
-import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_harness import check_walks_against_oracle, with_ceiling_blocker
 from restir_amd import params as P
 from restir_amd import scenes
-from restir_amd.renderer import Renderer
 
 pytestmark = pytest.mark.gpu
 
@@ -25,69 +24,17 @@ PAIRS = [(1, 1), (2, 1), (3, 1), (32, 1), (2, 0), (0, 1), (2, 2)]
 SHAPES = [("c2", 64, 64), ("c2", 50, 38), ("blocker", 50, 38), ("big_lights", 50, 38)]
 
 
-def _blocker(sc):
-    """sc with a quad 5 mm under the ceiling lights (z = 1.985), facing down, one more white material."""
-    z = 1.98
-    p = np.array([[-0.97, -0.97, z, -0.97, 0.97, z, 0.97, 0.97, z],
-                  [-0.97, -0.97, z, 0.97, 0.97, z, 0.97, -0.97, z]], np.float32)
-    n = np.tile(np.array([0, 0, -1], np.float32), (2, 3))
-    mats = list(sc.materials) + [scenes.Material(kd=(0.73, 0.73, 0.73), type=scenes.LAMBERT, shininess=1.0)]
-    return scenes.Scene(positions=np.concatenate([sc.positions, p]), normals=np.concatenate([sc.normals, n]),
-                        tri_material=np.concatenate([sc.tri_material, np.full(2, len(mats) - 1, np.uint32)]),
-                        materials=mats, camera=sc.camera, name="c2_64_blocker")
-
-
 @pytest.fixture(scope="module")
 def world():
     """name -> (scene, its oracle scene), built once"""
     sc = {"c2": scenes.cornell_many_lights(64), "big_lights": scenes.cornell_many_lights(64, size=0.2)}
-    sc["blocker"] = _blocker(sc["c2"])
+    sc["blocker"] = with_ceiling_blocker(sc["c2"], "c2_64_blocker")
     return {k: (v, O.OracleScene(v)) for k, v in sc.items()}
-
-
-def _cam(sc, f):
-    return scenes.orbit_camera(sc.camera, f, 48, 0.2)
-
-
-def _gpu(sc, W, H, prm, walk):
-    """(frames, reservoirs after the last frame, rays of all frames) with the walks pinned to `walk`"""
-    g = Renderer(W, H)
-    g.set_traversal(walk)
-    g.set_initial_split("off")
-    gs = g.load_scene(sc)
-    frames, rays = [], 0
-    for f in range(N_FRAMES):
-        frames.append(g.produce_restir(gs, _cam(sc, f), prm, f).copy())
-        rays += int(g.last_times.rays)
-    assert g.initial_split()[1] is False, "the last frame's initial pass ran candidate-split"
-    assert g.traversal()[1] == (0 if walk == "lockstep" else 1), "the last frame did not walk as pinned"
-    res = g.reservoirs()
-    gs.close()
-    g.close()
-    return frames, res, rays
-
-
-def _oracle(sc, osc, W, H, prm):
-    o = O.OracleRenderer(W, H)
-    return [o.render(osc, _cam(sc, f), prm, f) for f in range(N_FRAMES)], o.reservoirs()
-
-
-def _same(a, b, what):
-    assert np.isfinite(a).all(), what
-    assert np.array_equal(a, b), f"{what}: {int(np.any(a != b, -1).sum())} px differ"
 
 
 def _check(world, which, W, H, prm, what):
     sc, osc = world[which]
-    fa, ra, na = _gpu(sc, W, H, prm, "lockstep")
-    fb, rb, nb = _gpu(sc, W, H, prm, "lane")
-    fo, ro = _oracle(sc, osc, W, H, prm)
-    for f in range(N_FRAMES):
-        _same(fa[f], fb[f], f"{what} frame {f}, lockstep vs per-lane")
-        _same(fa[f], fo[f], f"{what} frame {f}, lockstep vs oracle")
-    _same(ra, rb, f"{what} reservoirs, lockstep vs per-lane")
-    _same(ra, ro, f"{what} reservoirs, lockstep vs oracle")
-    assert na == nb and na > 0, f"{what}: {na} rays in lockstep, {nb} per lane"
+    check_walks_against_oracle(sc, osc, W, H, prm, what, N_FRAMES)
 
 
 @pytest.mark.parametrize("m_area,m_brdf", PAIRS)

@@ -12,6 +12,7 @@ tests/test_gpu_light_lds.py does: AUTO runs frames this small through k_gbuffer_
 import numpy as np
 import pytest
 
+import gpu_harness as GH
 import oracle_lib as O
 from restir_amd import params as P
 from restir_amd import scenes
@@ -22,21 +23,8 @@ pytestmark = pytest.mark.gpu
 N_RAYS = 4096 + 37          # a partial last wave
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _c2_blocker():
-    """C2 with a quad 5 mm under the ceiling lights (z = 1.985), facing down, one more white material."""
-    sc = scenes.cornell_many_lights(1024)
-    z = 1.98
-    p = np.array([[-0.97, -0.97, z, -0.97, 0.97, z, 0.97, 0.97, z],
-                  [-0.97, -0.97, z, 0.97, 0.97, z, 0.97, -0.97, z]], np.float32)
-    n = np.tile(np.array([0, 0, -1], np.float32), (2, 3))
-    mats = list(sc.materials) + [scenes.Material(kd=(0.73, 0.73, 0.73), type=scenes.LAMBERT, shininess=1.0)]
-    return scenes.Scene(positions=np.concatenate([sc.positions, p]), normals=np.concatenate([sc.normals, n]),
-                        tri_material=np.concatenate([sc.tri_material, np.full(2, len(mats) - 1, np.uint32)]),
-                        materials=mats, camera=sc.camera, name="c2_blocker")
+def _with_blocker():
+    return GH.with_ceiling_blocker(scenes.cornell_many_lights(1024), "c2_blocker")
 
 
 def _one_triangle():
@@ -77,7 +65,7 @@ def _check_queries(sc, o, d, tnear, tfar_any, tfar_closest=3.0e38):
         _, anyg = g.debug_trace(gs, o, d, tn, tfar_any, any_hit=True, lockstep=lockstep)
         out[lockstep] = (t, prim, anyg)
         assert np.array_equal(prim, pr), f"closest prim vs oracle (lockstep={lockstep})"
-        assert np.array_equal(_bits(t), _bits(tr)), f"closest t vs oracle (lockstep={lockstep})"
+        assert np.array_equal(GH.bits(t), GH.bits(tr)), f"closest t vs oracle (lockstep={lockstep})"
         assert np.array_equal(anyg, anyr), f"any-hit vs oracle (lockstep={lockstep})"
     for a, b in zip(out[True], out[False]):
         assert np.array_equal(a, b), "lockstep vs per-lane"
@@ -88,7 +76,7 @@ def _check_queries(sc, o, d, tnear, tfar_any, tfar_closest=3.0e38):
 
 @pytest.mark.parametrize("blocker", [True, False], ids=["c2_blocker", "c2"])
 def test_shadow_and_primary_queries(blocker):
-    sc = _c2_blocker() if blocker else scenes.cornell_many_lights(1024)
+    sc = _with_blocker() if blocker else scenes.cornell_many_lights(1024)
     o, d, tf, to_wall = _shadow_rays(sc, np.random.default_rng(5))
     _, occ = _check_queries(sc, o, d, 0.01, tf)
     if blocker:    # the quad stops every ceiling-bound ray; wall-bound rays of the same waves mostly go on to the end
@@ -121,17 +109,13 @@ def _frames(sc, W, H, prm, walk, n_frames=3):
     import torch
     from restir_amd.distributed import _CudaBuf
     torch.cuda.set_stream(torch.cuda.Stream())        # the clones below are ordered on the frames' stream
-    g = Renderer(W, H, stream=torch.cuda.current_stream().cuda_stream)
-    g.set_traversal(walk)
-    g.set_initial_split("off")
-    g.set_run_ahead(2)
+    g = GH.pinned_renderer(W, H, walk, run_ahead=2, stream=torch.cuda.current_stream().cuda_stream)
     gs = g.load_scene(sc)
     frames = []
     for f in range(n_frames):
-        g.produce_restir(gs, scenes.orbit_camera(sc.camera, f, 48, 0.2), prm, f, copy_out=False, timed=False)
+        g.produce_restir(gs, GH.orbit_cam(sc, f), prm, f, copy_out=False, timed=False)
         frames.append(torch.as_tensor(_CudaBuf(g.frame_device_ptr(), W * H * 12, "<f4", 4), device="cuda").clone())
-    assert g.initial_split()[1] is False, "the last frame's initial pass ran candidate-split"
-    assert g.traversal()[1] == (0 if walk == "lockstep" else 1), "the last frame did not walk as pinned"
+    GH.assert_walked(g, walk)
     out = [t.cpu().numpy().reshape(H, W, 3) for t in frames], g.reservoirs()
     gs.close()
     g.close()
@@ -140,7 +124,7 @@ def _frames(sc, W, H, prm, walk, n_frames=3):
 
 @pytest.fixture(scope="module")
 def frame_scenes():
-    return {"c2_blocker": _c2_blocker(), "c2": scenes.cornell_many_lights(1024)}
+    return {"c2_blocker": _with_blocker(), "c2": scenes.cornell_many_lights(1024)}
 
 
 @pytest.mark.parametrize("m_area", [32, 3])                   # 3: the last candidate pair has one inactive ray
@@ -154,7 +138,5 @@ def test_frames_and_reservoirs_equal_per_lane(frame_scenes, which, W, H, m_area)
     fb, rb = _frames(sc, W, H, prm, "lane")
     for f, (a, b) in enumerate(zip(fa, fb)):
         assert np.isfinite(a).all()
-        d = (_bits(a) != _bits(b)).any(-1)
-        assert not d.any(), f"frame {f}: {int(d.sum())} px differ between lockstep and per-lane walks"
-    d = (_bits(ra) != _bits(rb)).any(-1)
-    assert not d.any(), f"reservoirs: {int(d.sum())} px differ"
+        GH.assert_same_bits(a, b, f"frame {f}, lockstep vs per-lane walks")
+    GH.assert_same_bits(ra, rb, "reservoirs, lockstep vs per-lane walks")

@@ -6,25 +6,14 @@ import numpy as np
 import pytest
 
 import material_cases as M
+from gpu_harness import assert_close
 from restir_amd import params as P
 from restir_amd import scenes
 from restir_amd.renderer import Renderer
 
 pytestmark = pytest.mark.gpu
 
-PIX_TOL, PIX_FRAC, MEAN_TOL = 1e-4, 0.995, 1e-4          # the project's frame bound (tests/test_gpu_parity.py:25)
 SIZE_IDS = [f"{w}x{h}" for w, h in M.SIZES]
-
-
-def _assert_close(gpu, ref, what):
-    """tests/test_gpu_parity.py's and tests/test_gpu_path.py's frame comparison"""
-    assert np.isfinite(gpu).all(), what
-    diff = np.linalg.norm(gpu.astype(np.float64) - ref, axis=-1)
-    rel = diff / np.maximum(np.linalg.norm(ref.astype(np.float64), axis=-1), 1e-3)
-    frac, mean = float((rel <= PIX_TOL).mean()), float(rel.mean())
-    print(f"[materials] {what}: {int((gpu != ref).any(axis=-1).sum())} of {rel.size} pixels not bit-identical, "
-          f"frac_ok={frac:.5f} mean_rel={mean:.3g} max_rel={rel.max():.3g}")
-    assert frac >= PIX_FRAC and mean <= MEAN_TOL, f"{what}: frac_ok={frac:.5f} mean_rel={mean:.3g} max_rel={rel.max():.3g}"
 
 
 # ---------------------------------------------------------------- 1. the type matrix
@@ -74,7 +63,7 @@ def test_mis_and_path_match_oracle(kind, size):
     want = (M.oracle_mis if kind == "mis" else M.oracle_path)(sc, size)
     for f in range(2):
         assert np.array_equal(out["lockstep"][f], out["lane"][f])
-        _assert_close(out["lane"][f], want[f], f"{kind} zoo frame {f}")
+        assert_close(out["lane"][f], want[f], f"{kind} zoo frame {f}", tag="materials")
 
 
 @pytest.mark.parametrize("m_brdf,classes", [(2, M.CLASSES), (0, M.CLASSES_NO_BRDF)], ids=["brdf2", "brdf0"])

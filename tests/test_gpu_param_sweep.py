@@ -15,20 +15,16 @@ made.
 import numpy as np
 import pytest
 
-import material_cases as M
+import gpu_harness as GH
 import param_cases as C
 from restir_amd import params as P
 from restir_amd.distributed import halo_rows
 from restir_amd.mgpu import MultiGpuFrame
 from restir_amd.renderer import Renderer, RestirError
-from test_gpu_path import _assert_close
-from test_gpu_skip_walks import KIND, _assert_walked
-from test_gpu_tiles import _emulate
 
 pytestmark = pytest.mark.gpu
 
 WALKS = ("lockstep", "lane")
-SORT_VARS = ("RESTIR_SORT", "RESTIR_SORT_SPATIAL", "RESTIR_SORT_TEMPORAL")
 NAN, INF = float("nan"), float("inf")
 ABOVE = float(np.nextafter(np.float32(P.MAX_SPATIAL_RADIUS), np.float32(INF)))
 REJECTED = [("spatial_radius", v) for v in (NAN, -1.0, -1e-30, -INF, INF, 1e20, ABOVE)] + \
@@ -50,21 +46,13 @@ def forms():
     def get(monkeypatch, size, walk, split="off", sort=None, ahead=None):
         key = (size, walk, split, sort, ahead)
         if key not in cache:
-            for k in SORT_VARS:
-                if sort is None:
-                    monkeypatch.delenv(k, raising=False)
-                else:
-                    monkeypatch.setenv(k, sort)
+            GH.set_env(monkeypatch, RESTIR_SORT=sort, RESTIR_SORT_SPATIAL=sort, RESTIR_SORT_TEMPORAL=sort)
             stream = None
             if ahead is not None:            # frames read on the device: a stream torch orders its clones on
                 import torch
                 streams.append(torch.cuda.Stream())
                 stream = streams[-1].cuda_stream
-            g = Renderer(*size, stream=stream)
-            g.set_traversal(walk)
-            g.set_initial_split(split)
-            if ahead is not None:
-                g.set_run_ahead(ahead)
+            g = GH.pinned_renderer(*size, walk, split, run_ahead=ahead, stream=stream)
             gs = g.load_scene(C.scene())
             assert gs.walk_info()["status"] == "live"
             cache[key] = (g, gs)
@@ -82,9 +70,9 @@ def _run(form, prm, walk, split="off"):
 
     def frame(h, cam, f):
         out = g.produce_restir(h, cam, prm, f)
-        _assert_walked(g, walk, split)
+        GH.assert_walked(g, walk, split)
         return out
-    return M.run_restir(g, gs, C.scene(), C.FRAMES, frame)
+    return GH.run_restir(g, gs, C.scene(), C.FRAMES, frame, C.camera)
 
 
 # ---------------------------------------------------------------- 1. one context, the whole table
@@ -92,14 +80,14 @@ def _run(form, prm, walk, split="off"):
 @pytest.mark.parametrize("case", C.ALL)
 def test_case_matches_oracle(case, walk, forms, oracle_runs, monkeypatch):
     got = _run(forms(monkeypatch, C.size(case), walk), C.params(case), walk)
-    M.assert_same_render(got, oracle_runs[case], f"{case} {walk}")
+    GH.assert_same_render(got, oracle_runs[case], f"{case} {walk}")
     if case in C.CONF_MAX:
         assert got.reservoirs[..., 11].max() == C.CONF_MAX[case]
 
 
 @pytest.mark.parametrize("walk", WALKS)
 def test_base_matches_oracle(walk, forms, oracle_runs, monkeypatch):
-    M.assert_same_render(_run(forms(monkeypatch, C.SIZE, walk), C.params(), walk), oracle_runs[None], f"base {walk}")
+    GH.assert_same_render(_run(forms(monkeypatch, C.SIZE, walk), C.params(), walk), oracle_runs[None], f"base {walk}")
 
 
 # ---------------------------------------------------------------- 2. the sorted passes pinned on and off
@@ -109,15 +97,15 @@ def test_sorted_passes_on_and_off(case, walk, forms, oracle_runs, monkeypatch):
     """RESTIR_SORT, RESTIR_SORT_SPATIAL and RESTIR_SORT_TEMPORAL all on and all off (BASE has CONSTANT weights and
     four neighbours, which the sorted spatial pass takes): equal to each other and to the oracle"""
     runs = {s: _run(forms(monkeypatch, C.SIZE, walk, sort=s), C.params(case), walk) for s in ("on", "off")}
-    M.assert_same_render(runs["on"], runs["off"], f"{case} {walk} sorted on vs off")
-    M.assert_same_render(runs["on"], oracle_runs[case], f"{case} {walk} sorted")
+    GH.assert_same_render(runs["on"], runs["off"], f"{case} {walk} sorted on vs off")
+    GH.assert_same_render(runs["on"], oracle_runs[case], f"{case} {walk} sorted")
 
 
 # ---------------------------------------------------------------- 3. the split initial pass and run-ahead
 @pytest.mark.parametrize("case", C.SPLIT_AHEAD)
 def test_initial_split(case, forms, oracle_runs, monkeypatch):
     got = _run(forms(monkeypatch, C.SIZE, "lockstep", split="on"), C.params(case), "lockstep", split="on")
-    M.assert_same_render(got, oracle_runs[case], f"{case} split")
+    GH.assert_same_render(got, oracle_runs[case], f"{case} split")
 
 
 @pytest.mark.parametrize("walk", WALKS)
@@ -134,17 +122,17 @@ def test_run_ahead(case, walk, forms, oracle_runs, monkeypatch):
     clones = []
     with torch.cuda.stream(stream):
         for f in range(C.FRAMES):
-            g.produce_restir(gs, M.camera(sc, f), prm, f, copy_out=False, timed=False)
+            g.produce_restir(gs, C.camera(sc, f), prm, f, copy_out=False, timed=False)
             clones.append(torch.as_tensor(_CudaBuf(g.frame_device_ptr(), w * h * 12, "<f4", 4), device="cuda").clone())
         frames = [c.cpu().numpy().reshape(h, w, 3) for c in clones]      # on the clones' stream: the copy waits for them
-    _assert_walked(g, walk)
-    got = M.Render(frames, g.gbuffer().copy(), g.reservoirs().copy())
-    M.assert_same_render(got, oracle_runs[case], f"{case} {walk} run-ahead 2")
+    GH.assert_walked(g, walk)
+    got = GH.Render(frames, g.gbuffer().copy(), g.reservoirs().copy())
+    GH.assert_same_render(got, oracle_runs[case], f"{case} {walk} run-ahead 2")
 
 
 # ---------------------------------------------------------------- 4. tiles and MultiGpuFrame
 def _cams():
-    return [M.camera(C.scene(), f) for f in range(C.FRAMES)]
+    return [C.camera(C.scene(), f) for f in range(C.FRAMES)]
 
 
 @pytest.fixture(scope="module")
@@ -156,7 +144,7 @@ def full_frames(forms):
         form = forms(mp, C.TILE_SIZE, "lockstep")
         for case in C.TILES:
             got = _run(form, C.params(case), "lockstep")
-            M.assert_same_render(got, C.oracle(case, C.TILE_SIZE), f"{case} at {C.TILE_SIZE}")
+            GH.assert_same_render(got, C.oracle(case, C.TILE_SIZE), f"{case} at {C.TILE_SIZE}")
             out[case] = got.frames
     finally:
         mp.undo()
@@ -171,7 +159,7 @@ def test_tiles_with_each_halo(case, n_ranks, full_frames):
     prm = C.params(case)
     if case in C.HALO:
         assert halo_rows(prm) == C.HALO[case]
-    tiles = _emulate(C.scene(), w, h, prm, n_ranks, _cams(), margin=0)
+    tiles = GH.emulate_tiles(C.scene(), w, h, prm, n_ranks, _cams(), margin=0)
     for f, (a, b) in enumerate(zip(tiles, full_frames[case])):
         assert np.array_equal(a, b), f"{case} {n_ranks} ranks frame {f}: {int((a != b).any(-1).sum())} px differ"
 
@@ -232,12 +220,12 @@ class _GpuTruths:
 
     def render_direct_mis(self, cam, prm, f, spp):
         out = self.g.render_direct_mis(self.gs, cam, prm, f, spp).copy()
-        assert self.g.traversal()[1] == KIND[self.walk]
+        assert self.g.traversal()[1] == GH.KIND[self.walk]
         return out
 
     def render_path(self, cam, prm, f, spp, **kw):
         out = self.g.render_path(self.gs, cam, prm, f, spp, **kw).copy()
-        assert self.g.traversal()[1] == KIND[self.walk]
+        assert self.g.traversal()[1] == GH.KIND[self.walk]
         return out
 
 
@@ -252,7 +240,7 @@ def test_ground_truths_with_moved_offsets():
         for f in range(C.GT_FRAMES):
             a, b = (C.ground_truth(kind, gpu[walk], prm, f) for walk in WALKS)
             assert np.array_equal(a, b), f"{kind} frame {f}: lockstep != lane"
-            _assert_close(a, want[kind][f], f"{kind} frame {f} with moved offsets")
+            GH.assert_close(a, want[kind][f], f"{kind} frame {f} with moved offsets", tag="path")
             assert (a == np.asarray(C.BG, np.float32)).all(-1).any()
 
 
@@ -272,7 +260,7 @@ def test_out_of_range_radius_and_cap_are_rejected(forms, oracle_runs, monkeypatc
             with pytest.raises(RestirError, match=field):
                 g.tile_begin(handle, cam, bad, f, 0, h, 0, 0)
         return g.produce_restir(handle, cam, C.params(), f)
-    M.assert_same_render(M.run_restir(g, gs, C.scene(), C.FRAMES, frame), oracle_runs[None], "base with rejected calls")
+    GH.assert_same_render(GH.run_restir(g, gs, C.scene(), C.FRAMES, frame, C.camera), oracle_runs[None], "base with rejected calls")
     # a radius is checked whether or not a spatial pass reads it
     with pytest.raises(RestirError, match="spatial_radius"):
         g.produce_restir(gs, C.scene().camera, P.default_params(spatial_radius=NAN), 0)

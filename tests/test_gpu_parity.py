@@ -16,27 +16,12 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_harness import assert_close, orbit_cam
 from restir_amd import params as P
 from restir_amd import scenes
 from restir_amd.renderer import Renderer, RestirError
 
 pytestmark = pytest.mark.gpu
-
-PIX_TOL, PIX_FRAC, MEAN_TOL = 1e-4, 0.995, 1e-4
-
-
-def _stats(gpu, ref):
-    diff = np.linalg.norm(gpu.astype(np.float64) - ref, axis=-1)
-    den = np.maximum(np.linalg.norm(ref.astype(np.float64), axis=-1), 1e-3)
-    rel = diff / den
-    return float((rel <= PIX_TOL).mean()), float(rel.mean()), float(rel.max())
-
-
-def _assert_close(gpu, ref, what=""):
-    assert np.isfinite(gpu).all(), what
-    frac, mean, mx = _stats(gpu, ref)
-    assert frac >= PIX_FRAC and mean <= MEAN_TOL, f"{what}: frac_ok={frac:.5f} mean_rel={mean:.3g} max_rel={mx:.3g}"
-
 
 def _pair(sc, W, H, prm, frames=1, cam=None):
     g = Renderer(W, H)
@@ -113,20 +98,20 @@ def test_initial_reservoirs_match_oracle():
     same_sample = np.all(ra[..., 0:9] == rb[..., 0:9], axis=-1)
     assert same_sample.mean() >= 0.995
     assert np.array_equal(ra[..., 11], rb[..., 11])          # confidence (capped)
-    _assert_close(*frames[0], "C2-like initial")
+    assert_close(*frames[0], "C2-like initial")
 
 
 # ---------------------------------------------------------------- frames
 def test_frame_c1_reference_defaults():
     sc = scenes.cornell_box(8)
     _, _, frames = _pair(sc, 128, 128, P.default_params())
-    _assert_close(*frames[0], "C1")
+    assert_close(*frames[0], "C1")
 
 
 def test_frame_c2_metric_point():
     sc = scenes.cornell_many_lights(1024)
     _, _, frames = _pair(sc, 192, 108, P.metric_params())
-    _assert_close(*frames[0], "C2 metric")
+    assert_close(*frames[0], "C2 metric")
 
 
 @pytest.mark.parametrize("mis", ["constant", "debias_contrib", "debias_z", "balance", "pairwise"])
@@ -134,7 +119,7 @@ def test_spatial_mis_modes(mis):
     sc = scenes.cornell_box(8)
     prm = P.default_params(m_area=4, do_spatial=1, spatial_neighbors=3, spatial_passes=2, spatial_mis=mis)
     _, _, frames = _pair(sc, 64, 48, prm)
-    _assert_close(*frames[0], mis)
+    assert_close(*frames[0], mis)
 
 
 @pytest.mark.parametrize("mis", ["constant", "debias_contrib", "debias_z", "balance", "pairwise"])
@@ -159,7 +144,7 @@ def test_temporal_spatial_sequence_moving_camera():
     cam = lambda f: scenes.orbit_camera(sc.camera, f, 24, 0.3)
     _, _, frames = _pair(sc, 96, 72, prm, frames=4, cam=cam)
     for i, (a, b) in enumerate(frames):
-        _assert_close(a, b, f"temporal frame {i}")
+        assert_close(a, b, f"temporal frame {i}")
 
 
 def test_visibility_pass_and_reject_dissimilar():
@@ -167,7 +152,7 @@ def test_visibility_pass_and_reject_dissimilar():
     prm = P.default_params(m_area=6, do_visibility_pass=1, do_spatial=1, spatial_neighbors=4, reject_dissimilar=1)
     _, _, frames = _pair(sc, 80, 60, prm, frames=2)
     for a, b in frames:
-        _assert_close(a, b, "visibility+reject")
+        assert_close(a, b, "visibility+reject")
 
 
 def test_phong_scene_c3_small():
@@ -176,7 +161,7 @@ def test_phong_scene_c3_small():
     cam = lambda f: scenes.orbit_camera(sc.camera, f, 240, 0.3)
     _, _, frames = _pair(sc, 96, 54, prm, frames=2, cam=cam)
     for a, b in frames:
-        _assert_close(a, b, "sponza-like")
+        assert_close(a, b, "sponza-like")
 
 
 @pytest.mark.parametrize("which", ["c2", "c3"])
@@ -205,7 +190,7 @@ def test_traversal_kinds_bit_identical(which):
         assert np.array_equal(frames["lockstep"][f], frames["auto"][f]), f"frame {f}: lockstep != auto"
     o, os_ = O.OracleRenderer(W, H), O.OracleScene(sc)
     for f in range(2):
-        _assert_close(frames["lane"][f], o.render(os_, cam(f), prm, f), f"{which} frame {f}")
+        assert_close(frames["lane"][f], o.render(os_, cam(f), prm, f), f"{which} frame {f}")
 
 
 @pytest.mark.parametrize("which", ["c2", "c3", "brdf2", "odd"])
@@ -242,7 +227,7 @@ def test_initial_split_bit_identical(which):
         for f in range(3):
             assert np.array_equal(ref[f], v[f]), f"{which} {k} frame {f}"
     o, os_ = O.OracleRenderer(W, H), O.OracleScene(sc)
-    _assert_close(out["lane", "on"][0], o.render(os_, cam(0), prm, 0), f"{which} split vs oracle")
+    assert_close(out["lane", "on"][0], o.render(os_, cam(0), prm, 0), f"{which} split vs oracle")
 
 
 @pytest.mark.parametrize("which", ["c2", "c3", "c5", "c5mix", "fused"])
@@ -255,7 +240,7 @@ def test_run_ahead_bit_identical(which):
     only cloned on the frames' stream (no host sync between frames), so the overlap really happens."""
     W, H = 96, 64
     upd = None
-    cam = lambda f: scenes.orbit_camera(sc.camera, f, 48, 0.2)
+    cam = lambda f: orbit_cam(sc, f)
     if which == "c2":
         sc, prm = scenes.cornell_many_lights(1024), P.metric_params()
     elif which == "c3":
@@ -297,7 +282,7 @@ def test_run_ahead_bit_identical(which):
     if which not in ("c5", "c5mix"):
         o, os_ = O.OracleRenderer(W, H), O.OracleScene(sc)
         for f in range(2):
-            _assert_close(out[2][f], o.render(os_, cam(f), prm, f), f"{which} run-ahead frame {f}")
+            assert_close(out[2][f], o.render(os_, cam(f), prm, f), f"{which} run-ahead frame {f}")
 
 
 def test_run_ahead_sequencing_bit_identical():
@@ -312,7 +297,7 @@ def test_run_ahead_sequencing_bit_identical():
     W, H, n_frames = 96, 64, 12
     sc, prm = scenes.cornell_many_lights(256), P.c3_params(m_area=6)
     assert prm.do_temporal and prm.do_spatial
-    cam = lambda f: scenes.orbit_camera(sc.camera, f, 48, 0.2)
+    cam = lambda f: orbit_cam(sc, f)
     depth_at = {0: 2, 6: 0, 8: 1, 10: 2}
     torch.cuda.set_stream(torch.cuda.Stream())       # the clones below are ordered on the frames' stream
     st = torch.cuda.current_stream().cuda_stream
@@ -379,7 +364,7 @@ def test_c5_moving_lights_match_oracle():
         a = g.produce_restir(gs, cam, prm, f).copy()
         moved = scenes.Scene(pos, sc.normals, sc.tri_material, sc.materials, sc.camera)
         b = o.render(O.OracleScene(moved), cam, prm, f)
-        _assert_close(a, b, f"C5 frame {f}")
+        assert_close(a, b, f"C5 frame {f}")
     assert gs.n_nodes > 0 and abs(gs.n_nodes - n_before) < n_before
     with pytest.raises(ValueError):
         gs.update_positions(np.zeros((3, 9), np.float32))
@@ -440,7 +425,7 @@ def test_direct_mis_matches_oracle(which):
         assert g.last_times.rays >= W * H
     for f in range(2):
         assert np.array_equal(out["lockstep"][f], out["lane"][f])
-        _assert_close(out["lane"][f], o.render_direct_mis(os_, sc.camera, prm, f, spp), f"MIS {which} frame {f}")
+        assert_close(out["lane"][f], o.render_direct_mis(os_, sc.camera, prm, f, spp), f"MIS {which} frame {f}")
 
 
 def test_direct_mis_leaves_restir_history_and_converges():
@@ -562,7 +547,7 @@ def test_odd_sizes(wh):
     prm = P.default_params(m_area=3, do_spatial=1, spatial_neighbors=2, do_temporal=1)
     _, _, frames = _pair(sc, wh[0], wh[1], prm, frames=2)
     for a, b in frames:
-        _assert_close(a, b, f"size {wh}")
+        assert_close(a, b, f"size {wh}")
 
 
 def test_no_emitters():
@@ -635,7 +620,7 @@ def test_obj_loader_matches_array_scene():
         a = g.produce_restir(gs_obj, sc.camera, P.default_params(), 0).copy()
     g2 = Renderer(48, 48)
     b = g2.produce_restir(g2.load_scene(sc), sc.camera, P.default_params(), 0)
-    _assert_close(a, b, "obj loader")
+    assert_close(a, b, "obj loader")
 
 
 def test_debug_reprojection_matches_oracle():
@@ -657,7 +642,7 @@ def test_debug_reprojection_matches_oracle():
         le_g, le_o = g.gbuffer()[..., 12:15], o.gbuffer()[..., 12:15]
         assert np.array_equal(le_g, le_o), f"frame {f}: {int(np.any(le_g != le_o, -1).sum())} G emissions differ"
         seen |= {tuple(map(float, v)) for v in le_g.reshape(-1, 3)} & colours
-        _assert_close(a, b, f"debug_reprojection frame {f}")
+        assert_close(a, b, f"debug_reprojection frame {f}")
         a0 = g0.produce_restir(gs0, c, prm0, f).copy()
         if f > 0:
             assert not np.array_equal(a, a0)          # the flag changes the picture

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from gpu_harness import assert_close
 import path_oracle as PO
 from restir_amd import params as P
 from restir_amd import scenes
@@ -18,20 +19,6 @@ from restir_amd.renderer import Renderer, RestirError, camera_desc, decode_image
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "restir-embree_amd", "restir_render")
-
-PIX_TOL, PIX_FRAC, MEAN_TOL = 1e-4, 0.995, 1e-4          # the project's frame bound (tests/test_gpu_parity.py:25)
-
-
-def _assert_close(gpu, ref, what):
-    assert np.isfinite(gpu).all(), what
-    diff = np.linalg.norm(gpu.astype(np.float64) - ref, axis=-1)
-    rel = diff / np.maximum(np.linalg.norm(ref.astype(np.float64), axis=-1), 1e-3)
-    frac, mean = float((rel <= PIX_TOL).mean()), float(rel.mean())
-    n_diff = int((gpu != ref).any(axis=-1).sum())
-    print(f"[path] {what}: {n_diff} of {rel.size} pixels not bit-identical, frac_ok={frac:.5f} mean_rel={mean:.3g} "
-          f"max_rel={rel.max():.3g}")
-    assert frac >= PIX_FRAC and mean <= MEAN_TOL, f"{what}: frac_ok={frac:.5f} mean_rel={mean:.3g} max_rel={rel.max():.3g}"
-
 
 # scene, params, W, H, spp, max_bounces, russian_roulette settings
 CASES = {
@@ -65,7 +52,7 @@ def test_path_matches_oracle(which):
         for f in range(2):
             assert np.array_equal(out["lockstep", rr][f], out["lane", rr][f])
             ref = PO.render_path(o, os_, sc.camera, prm, f, spp, max_bounces=mb, russian_roulette=rr)
-            _assert_close(out["lane", rr][f], ref, f"{which} rr={int(rr)} frame {f}")
+            assert_close(out["lane", rr][f], ref, f"{which} rr={int(rr)} frame {f}", tag="path")
     if len(rrs) > 1:
         differ = (out["lane", True][0] != out["lane", False][0]).any(axis=-1).mean()
         print(f"[path] {which}: roulette changes {100 * differ:.1f} % of the pixels")

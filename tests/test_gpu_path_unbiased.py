@@ -13,6 +13,7 @@ import pytest
 import closed_form as CF
 import closed_form_unbiased as CU
 import oracle_lib as O
+from gpu_harness import assert_close
 import path_oracle as PO
 from restir_amd import params as P
 from restir_amd import scenes
@@ -21,8 +22,6 @@ from restir_amd.renderer import Renderer, RestirError, camera_desc, decode_image
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOOL = os.path.join(ROOT, "restir-embree_amd", "restir_render")
-
-PIX_TOL, PIX_FRAC, MEAN_TOL = 1e-4, 0.995, 1e-4          # the sky case's bound: tests/test_gpu_path.py:22
 
 
 def _quad_prm():
@@ -92,13 +91,7 @@ def test_sky_and_maps_match_checker():
     for f in range(2):
         gpu = g.render_path(gs, sc.camera, prm, f, 2, max_bounces=3, unbiased=True).copy()
         ref = PO.render_path(o, os_, sc.camera, prm, f, 2, max_bounces=3, unbiased=True)
-        assert np.isfinite(gpu).all()
-        diff = np.linalg.norm(gpu.astype(np.float64) - ref, axis=-1)
-        rel = diff / np.maximum(np.linalg.norm(ref.astype(np.float64), axis=-1), 1e-3)
-        frac, mean = float((rel <= PIX_TOL).mean()), float(rel.mean())
-        print(f"[unbiased] textured frame {f}: {int((gpu != ref).any(axis=-1).sum())} of {rel.size} pixels not "
-              f"bit-identical, frac_ok={frac:.5f} mean_rel={mean:.3g} max_rel={rel.max():.3g}")
-        assert frac >= PIX_FRAC and mean <= MEAN_TOL
+        assert_close(gpu, ref, f"textured frame {f}", tag="unbiased")
 
 
 # ---------------------------------------------------------------- closed forms, never reading the checker

@@ -16,111 +16,20 @@ import numpy as np
 import pytest
 
 import bvh_brute as B
-import oracle_lib as O
+import gpu_harness as GH
+import skip_walk_cases as S
 from restir_amd import params as P
 from restir_amd import scenes
-from restir_amd.renderer import Renderer
+from gpu_harness import KIND, WALKS
+from skip_walk_cases import SIZE, oracle_frames, scns  # noqa: F401  (module-scoped fixtures)
 
 pytestmark = pytest.mark.gpu
 
-KIND = {"lockstep": 0, "lane": 1}
-WALKS = ["lane", "lockstep"]
-SIZE = {"c2": (64, 48), "c3": (64, 40)}          # 40 rows: a partial 16-row tile
-
-
-@pytest.fixture(scope="module")
-def scns():
-    return {"c2": scenes.cornell_many_lights(256), "c3": scenes.sponza_like(target_tris=30_000, n_lamps=128)}
-
-
-def _cam(sc, f):
-    return scenes.orbit_camera(sc.camera, f, 48, 0.2)
-
-
-def _load(monkeypatch, W, H, sc, walk, wide, split="off", sort=None, status="live", bvh=None):
-    """a renderer and the scene loaded with (wide = None) or without (wide = "off") the 8-wide tree, by the default
-    builder or (bvh = "lbvh") the Karras LBVH; the state is asserted"""
-    for k, v in (("RESTIR_WIDE", wide), ("RESTIR_BVH", bvh)):
-        if v is None:
-            monkeypatch.delenv(k, raising=False)
-        else:
-            monkeypatch.setenv(k, v)
-    for k in ("RESTIR_SORT", "RESTIR_SORT_SPATIAL", "RESTIR_SORT_TEMPORAL"):
-        if sort is None:
-            monkeypatch.delenv(k, raising=False)
-        else:
-            monkeypatch.setenv(k, sort)
-    g = Renderer(W, H)
-    g.set_traversal(walk)
-    g.set_initial_split(split)
-    gs = g.load_scene(sc)
-    info = gs.walk_info()
-    if wide == "off":
-        assert info["status"] == "off" and info["wide_nodes"] == 0 and gs.wide_tree() is None, info
-    else:
-        assert info["status"] == status and (info["wide_nodes"] > 0) == (status == "live"), info
-    if bvh == "lbvh":       # a valid tree with the LBVH's leaf maximum whose words are not the default builder's
-        nodes, prims = gs.bvh_tree()
-        B.check_bvh_tree(nodes, prims, sc.positions, 4)
-        monkeypatch.delenv("RESTIR_BVH")
-        ref = g.load_scene(sc)
-        monkeypatch.setenv("RESTIR_BVH", "lbvh")
-        rn, _ = ref.bvh_tree()
-        ref.close()
-        assert rn.shape != nodes.shape or not np.array_equal(rn.view(np.uint32), nodes.view(np.uint32)), \
-            "RESTIR_BVH=lbvh built the default builder's tree"
-    return g, gs
-
-
-def _assert_walked(g, walk, split="off"):
-    assert g.traversal()[1] == KIND[walk], "the last frame did not walk as pinned"
-    assert g.initial_split()[1] is (split == "on"), "the last frame's initial pass: split state not as pinned"
-
-
-def _sequence(monkeypatch, sc, W, H, walk, wide, prms, split="off", sort=None, bvh=None):
-    """one frame per entry of prms (frame index = position, orbiting camera): frames, ray counts, final reservoirs
-    and G-buffer"""
-    g, gs = _load(monkeypatch, W, H, sc, walk, wide, split, sort, bvh=bvh)
-    frames, rays = [], []
-    for f, prm in enumerate(prms):
-        frames.append(g.produce_restir(gs, _cam(sc, f), prm, f, timed=True).copy())
-        rays.append(int(g.last_times.rays))
-        _assert_walked(g, walk, split)
-    out = {"frames": frames, "rays": rays, "res": g.reservoirs().copy(), "gb": g.gbuffer().copy()}
-    gs.close()
-    g.close()
-    return out
-
-
-def _same_runs(a, b, what):
-    for f, (x, y) in enumerate(zip(a["frames"], b["frames"])):
-        assert np.isfinite(x).all(), f"{what} frame {f}"
-        assert np.array_equal(x, y), f"{what} frame {f}: {int((x != y).any(-1).sum())} px differ from the wide-tree run"
-    assert a["rays"] == b["rays"], f"{what}: rays {a['rays']} vs {b['rays']}"
-    assert np.array_equal(a["res"], b["res"], equal_nan=True), f"{what}: reservoirs differ"
-    assert np.array_equal(a["gb"], b["gb"], equal_nan=True), f"{what}: G-buffer differs"
-
-
 def _both(monkeypatch, sc, W, H, walk, prms, what, **kw):
-    off = _sequence(monkeypatch, sc, W, H, walk, "off", prms, **kw)
-    live = _sequence(monkeypatch, sc, W, H, walk, None, prms, **kw)
-    _same_runs(off, live, what)
+    off = S.sequence(monkeypatch, sc, W, H, walk, "off", prms, **kw)
+    live = S.sequence(monkeypatch, sc, W, H, walk, None, prms, **kw)
+    S.same_runs(off, live, what)
     return off
-
-
-def _base_prms(m_area=8):
-    return [P.c3_params(m_area=m_area)] * 3 + [P.c3_params(m_area=m_area, do_visibility_pass=1)]
-
-
-@pytest.fixture(scope="module")
-def oracle_frames(scns):
-    """the oracle's frames of the base sequence, once per scene"""
-    out = {}
-    for which, sc in scns.items():
-        W, H = SIZE[which]
-        o, os_ = O.OracleRenderer(W, H), O.OracleScene(sc)
-        out[which] = [o.render(os_, _cam(sc, f), prm, f).copy() for f, prm in enumerate(_base_prms())]
-    return out
 
 
 @pytest.mark.parametrize("walk", WALKS)
@@ -128,8 +37,8 @@ def oracle_frames(scns):
 def test_temporal_spatial_visibility(scns, oracle_frames, which, walk, monkeypatch):
     """three temporal + spatial frames, then a visibility-pass frame; also against the oracle, bit for bit"""
     sc, (W, H) = scns[which], SIZE[which]
-    off = _both(monkeypatch, sc, W, H, walk, _base_prms(), f"{which} {walk}")
-    for f, (a, b) in enumerate(zip(off["frames"], oracle_frames[which])):
+    off = _both(monkeypatch, sc, W, H, walk, S.base_prms(), f"{which} {walk}")
+    for f, (a, b) in enumerate(zip(off.frames, oracle_frames[which])):
         assert np.array_equal(a, b), f"{which} {walk} frame {f}: {int((a != b).any(-1).sum())} px differ from the oracle"
 
 
@@ -138,9 +47,9 @@ def test_sorted_passes_lane(scns, m_area, monkeypatch):
     """RESTIR_SORT, RESTIR_SORT_SPATIAL and RESTIR_SORT_TEMPORAL on with per-lane walks and no wide tree: the three
     `else` arms of `if constexpr (trav_lane(T) && trav_wide(T))` in rs_passes.h"""
     sc, (W, H) = scns["c3"], SIZE["c3"]
-    srt = _both(monkeypatch, sc, W, H, "lane", _base_prms(m_area), f"sorted a{m_area}", sort="on")
-    plain = _sequence(monkeypatch, sc, W, H, "lane", "off", _base_prms(m_area), sort="off")
-    _same_runs(srt, plain, f"sorted vs per-candidate a{m_area}")
+    srt = _both(monkeypatch, sc, W, H, "lane", S.base_prms(m_area), f"sorted a{m_area}", sort="on")
+    plain = S.sequence(monkeypatch, sc, W, H, "lane", "off", S.base_prms(m_area), sort="off")
+    S.same_runs(srt, plain, f"sorted vs per-candidate a{m_area}")
 
 
 @pytest.mark.parametrize("walk", WALKS)
@@ -173,12 +82,12 @@ def test_ground_truths(scns, walk, monkeypatch):
     prm = P.c3_params()
     out = {}
     for wide in ("off", None):
-        g, gs = _load(monkeypatch, W, H, sc, walk, wide)
+        g, gs = S.load(monkeypatch, W, H, sc, walk, wide)
         fr = []
         for f in range(2):
-            fr.append((g.render_direct_mis(gs, _cam(sc, f), prm, f, 2, timed=True).copy(), int(g.last_times.rays)))
+            fr.append((g.render_direct_mis(gs, GH.orbit_cam(sc, f), prm, f, 2, timed=True).copy(), int(g.last_times.rays)))
             assert g.traversal()[1] == KIND[walk]
-            fr.append((g.render_path(gs, _cam(sc, f), prm, f, 2, max_bounces=3, timed=True).copy(), int(g.last_times.rays)))
+            fr.append((g.render_path(gs, GH.orbit_cam(sc, f), prm, f, 2, max_bounces=3, timed=True).copy(), int(g.last_times.rays)))
             assert g.traversal()[1] == KIND[walk]
         out[wide] = fr
         gs.close()
@@ -199,10 +108,8 @@ def test_update_positions_binary_refit_alone(scns, which, walk, monkeypatch):
     structural checker after the amplitude-0.4 motion and again after rs_scene_rebuild."""
     sc, (W, H) = scns[which], SIZE[which]
     prm = P.c3_params(m_area=8)
-    g, gs = _load(monkeypatch, W, H, sc, walk, "off")
-    f_ = Renderer(W, H)
-    f_.set_traversal(walk)
-    f_.set_initial_split("off")
+    g, gs = S.load(monkeypatch, W, H, sc, walk, "off")
+    f_ = GH.pinned_renderer(W, H, walk)
     plan = [(0, 0.05, False), (40, 0.05, True), (90, 0.4, False), (130, 0.4, True)]
     n0, p0 = gs.bvh_tree()
     B.check_bvh_tree(n0, p0, sc.positions, 8)
@@ -215,7 +122,7 @@ def test_update_positions_binary_refit_alone(scns, which, walk, monkeypatch):
         assert gs.walk_info() == {"wide_nodes": 0, "wide_depth": -1, "status": "off"}, f"after update {f}"
         cam = scenes.orbit_camera(sc.camera, f, 240, 0.3)
         a = g.produce_restir(gs, cam, prm, f).copy()
-        _assert_walked(g, walk)
+        GH.assert_walked(g, walk)
         fresh = f_.load_scene(scenes.Scene(pos, sc.normals, sc.tri_material, sc.materials, sc.camera))
         assert fresh.walk_info()["status"] == "off"
         b = f_.produce_restir(fresh, cam, prm, f).copy()
@@ -251,16 +158,16 @@ def test_nonfinite_vertex_falls_back_in_frames(scns, monkeypatch):
     sc, (W, H) = scns["c2"], SIZE["c2"]
     nan_sc = _with_extra_triangle(sc, [0.1, 0.2, 0.3, np.nan, 0.1, 0.5, 0.4, 0.3, 0.9])
     zero_sc = _with_extra_triangle(sc, np.zeros(9))
-    prms = _base_prms()
+    prms = S.base_prms()
     out = {}
     for walk in WALKS:
-        g, gs = _load(monkeypatch, W, H, nan_sc, walk, None, status="nonfinite")
-        out[walk] = [g.produce_restir(gs, _cam(sc, f), prm, f).copy() for f, prm in enumerate(prms)]
-        _assert_walked(g, walk)
+        g, gs = S.load(monkeypatch, W, H, nan_sc, walk, None, status="nonfinite")
+        out[walk] = [g.produce_restir(gs, GH.orbit_cam(sc, f), prm, f).copy() for f, prm in enumerate(prms)]
+        GH.assert_walked(g, walk)
         gs.close()
         g.close()
-    g, gs = _load(monkeypatch, W, H, zero_sc, "lane", None)
-    ref = [g.produce_restir(gs, _cam(sc, f), prm, f).copy() for f, prm in enumerate(prms)]
+    g, gs = S.load(monkeypatch, W, H, zero_sc, "lane", None)
+    ref = [g.produce_restir(gs, GH.orbit_cam(sc, f), prm, f).copy() for f, prm in enumerate(prms)]
     gs.close()
     g.close()
     for f in range(len(prms)):

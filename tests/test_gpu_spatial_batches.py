@@ -13,14 +13,13 @@ skipped.  Frames of 50 x 38 (no multiple of the 8 x 8 wave tile) and 64 x 64; tw
 launch k_spatial<T, CM, 1>; the band case drives the same kernel through the tile stages.  The walk kind is pinned and
 asserted after the frames, as tests/test_gpu_lockstep_step.py does.
 """
-import numpy as np
 import pytest
 
+import gpu_harness as GH
 import oracle_lib as O
 from restir_amd import params as P
 from restir_amd import scenes
 from restir_amd.distributed import GpuTileBackend, band_rows, halo_rows
-from restir_amd.renderer import Renderer
 
 pytestmark = pytest.mark.gpu
 
@@ -36,61 +35,15 @@ def world():
     return {k: (v, O.OracleScene(v)) for k, v in sc.items()}
 
 
-def _cam(sc, f):
-    return scenes.orbit_camera(sc.camera, f, 48, 0.2)
-
-
 def _prm(**kw):
     """the metric point with three area candidates (the initial pass is not what these cases are about)"""
     return P.metric_params(m_area=3, m_brdf=1, **kw)
 
 
-def _gpu(sc, W, H, prm, walk):
-    """(frames, reservoirs after the last frame, rays of all frames) with the walks pinned to `walk`"""
-    g = Renderer(W, H)
-    g.set_traversal(walk)
-    g.set_initial_split("off")
-    gs = g.load_scene(sc)
-    frames, rays = [], 0
-    for f in range(N_FRAMES):
-        frames.append(g.produce_restir(gs, _cam(sc, f), prm, f).copy())
-        rays += int(g.last_times.rays)
-    assert g.initial_split()[1] is False, "the last frame's initial pass ran candidate-split"
-    assert g.traversal()[1] == (0 if walk == "lockstep" else 1), "the last frame did not walk as pinned"
-    res = g.reservoirs()
-    gs.close()
-    g.close()
-    return frames, res, rays
-
-
-def _oracle(sc, osc, W, H, prm):
-    """(frames, reservoirs after the last frame, rays of all frames)"""
-    o = O.OracleRenderer(W, H)
-    frames, rays = [], 0
-    for f in range(N_FRAMES):
-        frames.append(o.render(osc, _cam(sc, f), prm, f))
-        rays += o.rays
-    return frames, o.reservoirs(), rays
-
-
-def _same(a, b, what):
-    assert np.isfinite(a).all(), what
-    assert np.array_equal(a, b), f"{what}: {int(np.any(a != b, -1).sum())} px differ"
-
-
 def _check(world, which, W, H, prm, what):
     """-> (rays of the lockstep kernels, rays of the oracle)"""
     sc, osc = world[which]
-    fa, ra, na = _gpu(sc, W, H, prm, "lockstep")
-    fb, rb, nb = _gpu(sc, W, H, prm, "lane")
-    fo, ro, no = _oracle(sc, osc, W, H, prm)
-    for f in range(N_FRAMES):
-        _same(fa[f], fb[f], f"{what} frame {f}, lockstep vs per-lane")
-        _same(fa[f], fo[f], f"{what} frame {f}, lockstep vs oracle")
-    _same(ra, rb, f"{what} reservoirs, lockstep vs per-lane")
-    _same(ra, ro, f"{what} reservoirs, lockstep vs oracle")
-    assert na == nb and na > 0, f"{what}: {na} rays in lockstep, {nb} per lane"
-    return na, no
+    return GH.check_walks_against_oracle(sc, osc, W, H, prm, what, N_FRAMES)
 
 
 @pytest.mark.parametrize("k", KS)
@@ -130,11 +83,12 @@ def test_full_size_launch(world):
     against per-lane only (the oracle would take seconds at this size)."""
     sc, _ = world["c2"]
     prm = _prm(spatial_neighbors=4)
-    fa, ra, na = _gpu(sc, 1280, 544, prm, "lockstep")
-    fb, rb, nb = _gpu(sc, 1280, 544, prm, "lane")
+    a = GH.gpu_frames(sc, 1280, 544, [prm] * N_FRAMES, "lockstep")
+    b = GH.gpu_frames(sc, 1280, 544, [prm] * N_FRAMES, "lane")
     for f in range(N_FRAMES):
-        _same(fa[f], fb[f], f"frame {f}, lockstep vs per-lane")
-    _same(ra, rb, "reservoirs, lockstep vs per-lane")
+        GH.assert_equal_finite(a.frames[f], b.frames[f], f"frame {f}, lockstep vs per-lane")
+    GH.assert_equal_finite(a.res, b.res, "reservoirs, lockstep vs per-lane")
+    na, nb = sum(a.rays), sum(b.rays)
     assert na == nb and na > 0, f"{na} rays in lockstep, {nb} per lane"
 
 
@@ -145,20 +99,17 @@ def test_band(world):
     sc, _ = world["c2"]
     W, H, n_ranks = 64, 64, 2
     prm = _prm(spatial_neighbors=4, do_visibility_pass=1, spatial_passes=2)
-    full, _, _ = _gpu(sc, W, H, prm, "lockstep")
+    full = GH.gpu_frames(sc, W, H, [prm] * N_FRAMES, "lockstep").frames
     torch.cuda.set_stream(torch.cuda.Stream())
     st = torch.cuda.current_stream().cuda_stream
-    rs = [Renderer(W, H, stream=st) for _ in range(n_ranks)]
-    for r in rs:
-        r.set_traversal("lockstep")
-        r.set_initial_split("off")
+    rs = [GH.pinned_renderer(W, H, "lockstep", stream=st) for _ in range(n_ranks)]
     bes = [GpuTileBackend(r) for r in rs]
     hs = [be.load_scene(sc) for be in bes]
     h = halo_rows(prm)
     for f in range(N_FRAMES):
         for r, be in enumerate(bes):
             y0, y1 = band_rows(H, r, n_ranks)
-            be.begin(hs[r], _cam(sc, f), prm, f, y0, y1, h, h)
+            be.begin(hs[r], GH.orbit_cam(sc, f), prm, f, y0, y1, h, h)
         for be in bes:
             be.temporal()
         for p in range(prm.spatial_passes):
@@ -171,6 +122,6 @@ def test_band(world):
         for r, be in enumerate(bes):
             y0, y1 = band_rows(H, r, n_ranks)
             band = be.finish().cpu().numpy().reshape(-1, W, 3)
-            _same(band, full[f][y0:y1], f"frame {f}, rows {y0}..{y1}")
+            GH.assert_equal_finite(band, full[f][y0:y1], f"frame {f}, rows {y0}..{y1}")
     for r in rs:
         assert r.traversal()[1] == 0, "a band did not walk as pinned"

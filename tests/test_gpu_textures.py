@@ -11,11 +11,11 @@ import pytest
 from PIL import Image
 
 import oracle_lib as O
+from gpu_harness import assert_close
+from image_files import rgbe_encode, write_hdr
 from restir_amd import params as P
 from restir_amd import scenes
 from restir_amd.renderer import Renderer
-from test_gpu_parity import _assert_close
-from test_image_io import _rgbe_encode, _write_hdr
 
 pytestmark = pytest.mark.gpu
 
@@ -57,12 +57,12 @@ def test_textured_frames_match_oracle():
         gs = g.load_scene(sc)
         for f in range(frames):
             cam = scenes.orbit_camera(sc.camera, f, 48, 0.3)
-            _assert_close(g.produce_restir(gs, cam, prm, f).copy(), o.render(o_s, cam, prm, f), f"textured frame {f}")
+            assert_close(g.produce_restir(gs, cam, prm, f).copy(), o.render(o_s, cam, prm, f), f"textured frame {f}")
     g = Renderer(W, H)
     gs = g.load_scene(sc)
     prm = P.default_params(use_skybox=1)
     o = O.OracleRenderer(W, H)
-    _assert_close(g.render_direct_mis(gs, sc.camera, prm, 0, 4).copy(), o.render_direct_mis(o_s, sc.camera, prm, 0, 4),
+    assert_close(g.render_direct_mis(gs, sc.camera, prm, 0, 4).copy(), o.render_direct_mis(o_s, sc.camera, prm, 0, 4),
                   "textured MIS")
 
 
@@ -120,8 +120,8 @@ def _write_obj(tmp, sc, jpeg=False):
         i = 3 * t + 1
         out.append(f"f {i}/{i}/{i} {i + 1}/{i + 1}/{i + 1} {i + 2}/{i + 2}/{i + 2}")
     (tmp / "scene.obj").write_text("\n".join(out) + "\n")
-    rgbe, sky = _rgbe_encode(sc.sky.data)
-    _write_hdr(tmp / "sky.hdr", rgbe, rle=True)
+    rgbe, sky = rgbe_encode(sc.sky.data)
+    write_hdr(tmp / "sky.hdr", rgbe, rle=True)
     if jpeg:
         return tmp / "scene.obj", tmp / "sky.hdr", sky, decoded
     return tmp / "scene.obj", tmp / "sky.hdr", sky

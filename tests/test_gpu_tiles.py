@@ -6,45 +6,12 @@ import os
 import numpy as np
 import pytest
 
+from gpu_harness import emulate_tiles, orbit_cam
 from restir_amd import params as P
 from restir_amd import scenes
-from restir_amd.distributed import GpuTileBackend, band_rows, halo_rows
 from restir_amd.renderer import Renderer
 
 pytestmark = pytest.mark.gpu
-
-
-def _emulate(sc, W, H, prm, n_ranks, cams, margin):
-    import torch
-    torch.cuda.set_stream(torch.cuda.Stream())      # a real (non-null) stream shared with the contexts
-    st = torch.cuda.current_stream().cuda_stream
-    bes = [GpuTileBackend(Renderer(W, H, stream=st)) for _ in range(n_ranks)]
-    hs = [be.load_scene(sc) for be in bes]
-    h = halo_rows(prm)
-    out = []
-    for f, cam in enumerate(cams):
-        for r, be in enumerate(bes):
-            y0, y1 = band_rows(H, r, n_ranks)
-            be.begin(hs[r], cam, prm, f, y0, y1, max(margin, h), h)
-        for be in bes:
-            be.temporal()
-        if prm.do_spatial:
-            for p in range(prm.spatial_passes):
-                torch.cuda.synchronize()
-                for r, be in enumerate(bes):
-                    if h == 0:                      # a radius below 1: no neighbour leaves its pixel, no halo rows
-                        assert all(be.halo_tensor(i) is None for i in range(4))
-                        continue
-                    if r > 0:
-                        be.halo_tensor(0).copy_(bes[r - 1].halo_tensor(3))
-                    if r < n_ranks - 1:
-                        be.halo_tensor(1).copy_(bes[r + 1].halo_tensor(2))
-                torch.cuda.synchronize()
-                for be in bes:
-                    be.spatial(p)
-        bands = [be.finish().cpu().numpy().reshape(-1, W, 3) for be in bes]
-        out.append(np.concatenate(bands, 0))
-    return out
 
 
 @pytest.mark.parametrize("n_ranks", [2, 4])
@@ -52,8 +19,8 @@ def test_tiles_bit_identical_to_full_frame(n_ranks):
     sc = scenes.cornell_many_lights(128)
     W, H = 96, 64
     prm = P.default_params(m_area=6, do_spatial=1, spatial_neighbors=4, spatial_passes=2, do_temporal=1)
-    cams = [scenes.orbit_camera(sc.camera, f, 48, 0.2) for f in range(3)]
-    tiles = _emulate(sc, W, H, prm, n_ranks, cams, margin=H)
+    cams = [orbit_cam(sc, f) for f in range(3)]
+    tiles = emulate_tiles(sc, W, H, prm, n_ranks, cams, margin=H)
     full = Renderer(W, H)
     fs = full.load_scene(sc)
     for f, cam in enumerate(cams):
@@ -65,7 +32,7 @@ def test_metric_point_tiles():
     sc = scenes.cornell_many_lights(1024)
     W, H = 128, 72
     prm = P.metric_params()
-    tiles = _emulate(sc, W, H, prm, 4, [sc.camera], margin=0)
+    tiles = emulate_tiles(sc, W, H, prm, 4, [sc.camera], margin=0)
     full = Renderer(W, H)
     ref = full.produce_restir(full.load_scene(sc), sc.camera, prm, 0)
     assert np.array_equal(tiles[0], ref)

@@ -16,18 +16,17 @@ import ctypes
 import numpy as np
 import pytest
 
+import bvh_brute as B
 import oracle_lib as O
 from restir_amd import params as P
 from restir_amd import scenes
 from restir_amd.renderer import Renderer
 
-import test_wide_bvh
-
 pytestmark = pytest.mark.gpu
 
 
 def _host_tree(pos):
-    L = test_wide_bvh._lib()
+    L = B.wide_lib()
     L.wide_build_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                   ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     pos = np.ascontiguousarray(pos, np.float32)
@@ -43,50 +42,15 @@ def _host_tree(pos):
     return words[:nn], prims[:npr.value], dep.value
 
 
-def _scene_from_positions(pos):
-    base = scenes.cornell_box(8)
-    n = pos.shape[0]
-    nrm = np.tile(np.array([0, 0, 1] * 3, np.float32), (n, 1))
-    return scenes.Scene(np.ascontiguousarray(pos, np.float32), nrm, np.zeros(n, np.uint32), base.materials[:1], base.camera)
-
-
-def _soup(n, seed, dup=0):
-    rng = np.random.default_rng(seed)
-    c = rng.uniform(-1, 1, (n, 1, 3)).astype(np.float32) * np.array([4, 2, 1.5], np.float32)
-    p = (c + rng.normal(scale=0.05, size=(n, 3, 3)).astype(np.float32)).reshape(n, 9)
-    if dup:
-        p[:dup] = p[0]                   # coincident triangles: every centroid equal in a > 256-triangle node
-    return p
-
-
-def _nonfinite():
-    p = _soup(800, 5)
-    p[17, 4] = np.nan                    # one NaN and one infinite coordinate
-    p[401, 0] = np.inf
-    return _scene_from_positions(p)
-
-
-def _chain(n, ratio):
-    """n triangles side by side along x, each `ratio` x the size of the previous: a binned / swept SAH split peels
-    off the largest triangle at every level, so the source tree is a chain of depth n - 1 (the SAH-optimal 8-wide
-    collapse of 100 such triangles needs exactly 8 levels; of 110, more than the walk's group stack holds)"""
-    pos, x = [], 0.0
-    for i in range(n):
-        sz = ratio ** i
-        pos.append([x, 0.0, 0.0, x + sz, 0.0, 0.0, x, sz, 0.0])
-        x += sz
-    return np.array(pos, np.float32)
-
-
 CASES = {
     "c2": lambda: scenes.cornell_many_lights(1024),
     "c3": lambda: scenes.sponza_like(),
-    "one": lambda: _scene_from_positions(_soup(1, 1)),
-    "three": lambda: _scene_from_positions(_soup(3, 2)),
-    "soup5k": lambda: _scene_from_positions(_soup(5000, 3)),
-    "coincident": lambda: _scene_from_positions(_soup(1500, 4, dup=700)),
-    "nonfinite": _nonfinite,             # ADVICE r3: the wide tree is optional -- the scene loads without one
-    "depth8": lambda: _scene_from_positions(_chain(100, 1.5)),   # exactly the walk's stack depth
+    "one": lambda: B.scene_from_positions(B.soup32(1, 1)),
+    "three": lambda: B.scene_from_positions(B.soup32(3, 2)),
+    "soup5k": lambda: B.scene_from_positions(B.soup32(5000, 3)),
+    "coincident": lambda: B.scene_from_positions(B.soup32(1500, 4, dup=700)),
+    "nonfinite": B.nonfinite_scene,      # the wide tree is optional -- the scene loads without one
+    "depth8": B.depth8_scene,            # exactly the walk's stack depth
 }
 
 
@@ -241,18 +205,18 @@ def test_c3_moving_lamps_on_live_wide_tree():
 
 
 def test_deep_tree_falls_back_to_skip_walks():
-    """a scene whose SAH-optimal collapse does not fit the walk's 8-level group stack (_chain(110)) loads
+    """a scene whose SAH-optimal collapse does not fit the walk's 8-level group stack (B.chain(110)) loads
     without a wide tree; rs_scene_walk_info says why (too_deep), the host restatement agrees (no plan within depth 8),
     and the per-lane walks -- on the skip pointers now -- return the lockstep walks' and the oracle's hits bit for
     bit.  The 100-triangle chain (depth exactly 8) keeps its tree (CASES["depth8"] above)."""
-    pos = _chain(110, 1.5)
+    pos = B.chain(110, 1.5)
     assert _host_tree(pos) is None
-    sc = _scene_from_positions(pos)
+    sc = B.scene_from_positions(pos)
     g = Renderer(8, 8)
     gs = g.load_scene(sc)
     assert gs.walk_info() == {"wide_nodes": 0, "wide_depth": -1, "status": "too_deep"}, gs.walk_info()
     assert gs.wide_tree() is None
-    ok = g.load_scene(_scene_from_positions(_chain(100, 1.5)))
+    ok = g.load_scene(B.scene_from_positions(B.chain(100, 1.5)))
     info = ok.walk_info()
     assert info["status"] == "live" and info["wide_depth"] == 8 and info["wide_nodes"] > 0, info
     # rays aimed at a random point of a random triangle from a scale-relative distance (every size class is hit;

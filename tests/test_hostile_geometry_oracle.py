@@ -17,12 +17,9 @@ import pytest
 
 import bvh_brute as B
 import oracle_lib as O
+from gpu_harness import bits
 
 AMBIGUOUS_CAP = 0.02        # a condition on the inputs, not a tolerance on the result
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module", params=B.CLASS_NAMES)
@@ -49,7 +46,7 @@ def test_oracle_equals_brute_force(case, wide):
     if cls.name != "huge":                      # the oracle may decline an 8-wide tree over 1e20 boxes
         assert os_.wide == wide
     t, prim = os_.trace_closest(o, d, float(cls.tnear), 3.0e38)
-    bad = np.flatnonzero((prim != pb) | (_bits(t) != _bits(tb)))
+    bad = np.flatnonzero((prim != pb) | (bits(t) != bits(tb)))
     assert bad.size == 0, f"{cls.name}: {bad.size} closest rays differ from brute force, first {bad[:5]}"
     anyh = os_.trace_any(ao, ad, atn, atf).astype(bool)
     bad = np.flatnonzero((anyh != aref) & ~amb)
@@ -65,7 +62,7 @@ def test_oracle_size_ladder(n):
     tb, pb = B.brute_closest(cls.positions, o, d, cls.tnear, 3.0e38)
     for wide in (False, True):
         t, prim = O.OracleScene(B.scene_from_positions(cls.positions), wide=wide).trace_closest(o, d, float(cls.tnear), 3.0e38)
-        assert np.array_equal(prim, pb) and np.array_equal(_bits(t), _bits(tb)), (n, wide)
+        assert np.array_equal(prim, pb) and np.array_equal(bits(t), bits(tb)), (n, wide)
 
 
 def test_checker_catches_broken_trees():

@@ -5,32 +5,15 @@ restated on the CPU with the same float operations -- closest hits (t, triangle,
 answers identical to brute force over all triangles, for random, axis-parallel and on-plane rays
 (tests/cpp/wide_harness.cpp)."""
 import ctypes
-import os
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "wide_harness.cpp")
-HDR = os.path.join(ROOT, "restir-embree_amd", "csrc", "rs_wide.h")
-SO = os.path.join(ROOT, "oracle", "_build", "libwide_harness.so")
-
-
-def _lib():
-    os.makedirs(os.path.dirname(SO), exist_ok=True)
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(SRC), os.path.getmtime(HDR)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-o", SO, SRC])
-    L = ctypes.CDLL(SO)
-    L.wide_check.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.c_char_p, ctypes.c_int,
-                             ctypes.c_int]
-    L.wide_query.argtypes = [ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
-    return L
-
+from bvh_brute import wide_lib
 
 @pytest.mark.parametrize("collapse", [0, 1, 2, 3], ids=["greedy", "sah", "sah-hostsah", "hostsah-coincident"])
 @pytest.mark.parametrize("n,seed", [(1, 1), (2, 2), (7, 3), (9, 4), (64, 5), (1000, 6), (20000, 7)])
 def test_wide_tree_structure_and_conservative_boxes(n, seed, collapse):
-    L = _lib()
+    L = wide_lib()
     msg = ctypes.create_string_buffer(256)
     depth = ctypes.c_int(-1)
     nn = L.wide_check(n, seed, ctypes.byref(depth), msg, 256, collapse)
@@ -41,7 +24,7 @@ def test_wide_tree_structure_and_conservative_boxes(n, seed, collapse):
 @pytest.mark.parametrize("collapse", [0, 1, 2, 3], ids=["greedy", "sah", "sah-hostsah", "hostsah-coincident"])
 @pytest.mark.parametrize("n,seed", [(1, 11), (5, 12), (300, 13), (5000, 14)])
 def test_wide_walk_matches_brute_force(n, seed, collapse):
-    L = _lib()
+    L = wide_lib()
     hits = ctypes.c_int(0)
     rc = L.wide_query(n, seed, 4000, ctypes.byref(hits), collapse)
     assert rc == 4000, f"ray {-rc - 1000} differs from brute force"
@@ -52,7 +35,7 @@ def test_nonfinite_geometry_builds_no_wide_tree():
     """non-finite vertices leave the scene without a wide tree (the walks take the skip pointers)
     instead of failing the load or sorting NaN centroids (tests/test_gpu_wide.py checks the GPU builder)."""
     import numpy as np
-    L = _lib()
+    L = wide_lib()
     L.wide_build_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                   ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
     rng = np.random.default_rng(2)
